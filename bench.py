@@ -2,7 +2,7 @@
 """Throughput of the batched multi-snake env step on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg3s8|cfg4|cfg5]
-                    [--scaling strong|weak]
+                    [--scaling strong|weak] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
 
 --gpus N > 1 without a launcher (no WORLD_SIZE in the environment) starts the N
@@ -29,7 +29,20 @@ share of the 8-GPU configuration, weak scaling by default):
 
 A step = one SnakeVecEnv.step() over the GPU's whole batch. The timed region is
 exactly K steps between barrier + synchronize on both sides; value = all envs of
-all ranks x K / the slowest rank's time.
+all ranks x K / the slowest rank's time; ms_per_step = that time / K.
+
+A plain run sets up, warms up, times the K steps and prints the JSON line. What
+takes a run of its own beside the timed steps (the CPU baseline) runs only with
+--full; without it `cpu_baseline` is null.
+
+--dump-outputs DIR writes what the last timed step returned to its caller, one
+DIR/<name>.npy per array (rank r > 0: <name>_rank<r>.npy): obs (float32),
+rewards (float64), dones, episode_done, rank, error (float32), episode_scores /
+_steps / _fruits / _kills (float64). At most 64 MB in all: obs holds the rows of
+a fixed sample of envs (numpy RandomState(0), sorted; obs_env_index.npy names
+them), and so do the per-env arrays (env_index.npy) should they not fit. The
+envs' seeds and the actions are fixed by the arguments, so two builds run with
+the same arguments can be compared array by array.
 
 A step is two launches on the caller's stream (include/snake_env.h snake_step):
 k_logic (rules, all envs), then k_post, whose first blocks are the reset workers
@@ -55,7 +68,7 @@ The JSON line also carries:
                   (fs+1)*H*W + 10*S bytes per env-step x envs /
                   ms_per_step.
   kernels      -- average device ms per launch of each step kernel (same events).
-  cpu_baseline -- rank 0 at N=1: the CPU restatement (oracle/, a C port of the
+  cpu_baseline -- with --full, rank 0 at N=1: the CPU restatement (oracle/, a C port of the
                   reference SnakeEnv) on every available host core (one process
                   per core, at most 16: the box's CPU share), a bounded sample of
                   the same workload, run BEFORE the GPU is touched; plus the
@@ -203,6 +216,48 @@ def cpu_baseline(env_kw, num_snakes, seconds, ratio_key):
     return out
 
 
+DUMP_OBS_BYTES = 32 << 20     # --dump-outputs: the observation sample
+DUMP_REST_BYTES = 24 << 20    # ... and every other array together (< 64 MB in all)
+
+
+def sample_rows(n, row_bytes, budget):
+    """Sorted indices of a fixed (seeded) sample of n rows whose row_bytes each
+    fit the budget; None when all n rows fit."""
+    k = max(1, budget // max(1, row_bytes))
+    if k >= n:
+        return None
+    import numpy as np
+    return np.sort(np.random.RandomState(0).choice(n, size=k, replace=False))
+
+
+def dump_outputs(path, rank, out):
+    """--dump-outputs: the (obs, rewards, dones, info) of one SnakeVecEnv.step as
+    float32 / float64 .npy files (see the module docstring)."""
+    import numpy as np
+    import torch
+    obs, rew, done, info = out
+    n = obs.shape[0]
+    rest = {'rewards': rew.double(), 'dones': done.float(), 'episode_done': info['episode_done'].float(),
+            'rank': info['rank'].float(), 'error': info['error'].float()}
+    for k in ('episode_scores', 'episode_steps', 'episode_fruits', 'episode_kills'):
+        rest[k] = info[k].double()
+    arrays = {}
+    idx = sample_rows(n, obs[0].numel() * 4, DUMP_OBS_BYTES)
+    if idx is not None:
+        arrays['obs_env_index'] = idx.astype(np.float64)
+        obs = obs[torch.from_numpy(idx).to(obs.device)]
+    arrays['obs'] = obs.float().cpu().numpy()
+    idx = sample_rows(n, sum(v[0].numel() * v.element_size() for v in rest.values()), DUMP_REST_BYTES)
+    if idx is not None:
+        arrays['env_index'] = idx.astype(np.float64)
+        sel = torch.from_numpy(idx).to(rew.device)
+        rest = {k: v[sel] for k, v in rest.items()}
+    arrays.update((k, v.cpu().numpy()) for k, v in rest.items())
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, f'{k}.npy' if rank == 0 else f'{k}_rank{rank}.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -226,8 +281,13 @@ def main():
                          'of up to 8 192 envs and 64 MiB of observations), 1 on, -1 off')
     ap.add_argument('--spawn-ahead', type=int, default=0,
                     help='snake_cfg.spawn_ahead: 0 default threshold, -1 off, k: envs with at most k live snakes')
-    ap.add_argument('--cpu-seconds', type=float, default=10.0)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what a plain run leaves out: the CPU baseline (before the GPU is touched)')
+    ap.add_argument('--cpu-seconds', type=float, default=10.0, help='length of the CPU baseline (--full)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write the arrays the last timed step returned as DIR/<name>.npy '
+                         '(float32 / float64, at most 64 MB: a fixed sample of the envs where they are larger)')
     ap.add_argument('--dist-backend', choices=('nccl', 'gloo'), default='nccl',
                     help='process group of the timing barrier / max-reduce (gloo: CPU tensors; '
                          'lets several ranks share one GPU, e.g. the two-rank test on a one-GPU box)')
@@ -244,6 +304,8 @@ def main():
                          '(0: none; default max(1, min(32, steps // 4)), so at least 4 launches are '
                          'averaged; a timed step costs ~1-2 us more: 0.1034 ms per step at stride 32 vs 0.1025 untimed, cfg3)')
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error('--dump-outputs needs at least one timed step')
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -257,7 +319,7 @@ def main():
                   vision_range=args.vision_range or None, frame_stack=args.frame_stack)
     S = args.num_snakes
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         key = None
         if (args.height, args.width, S, args.frame_stack) == (20, 20, 4, 1) and args.vision_range in (0, 5):
             key = 'cfg3_20x20_s4_vr5' if args.vision_range else 'cfg2_20x20_s4_full'
@@ -302,8 +364,10 @@ def main():
 
     # (outputs are dropped at once unless --dump-dir sums them: holding a step's
     # outputs while the next step runs makes the allocator alternate between two
-    # observation buffers; measured +4 us per step at cfg3)
+    # observation buffers; measured +4 us per step at cfg3. --dump-outputs keeps
+    # the last timed step's alone)
     out = None
+    last = args.steps - 1 if args.dump_outputs else -1
     L = _native.lib()
     for t in range(args.warmup):
         # the last --timing-warm warmup steps are timed and their timings dropped:
@@ -333,11 +397,12 @@ def main():
         timed = stride > 0 and t % stride == 0
         if timed:
             _native.timing_enable(True, L)
-        if rsum is None:
+        if rsum is None and t != last:
             venv.step(actions[args.warmup + t])
         else:
             out = venv.step(actions[args.warmup + t])
-            rsum += out[1]
+            if rsum is not None:
+                rsum += out[1]
         if timed:
             _native.timing_enable(False, L)
     torch.cuda.synchronize(device)
@@ -445,6 +510,8 @@ def main():
                  grids=venv.grids().cpu().numpy(), mt=keys.cpu().numpy(), mt_pos=pos.cpu().numpy(),
                  env=venv.env_records().cpu().numpy(), obs=out[0].cpu().numpy(),
                  rew_sum=rsum.cpu().numpy())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, out)
     if rank == 0:
         print(json.dumps(line), flush=True)
     if distributed:

@@ -18,7 +18,7 @@ if [ "${TESTS:-0}" = 1 ]; then
   run tests 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread
 fi
 if [ "${BENCH:-1}" = 1 ]; then
-  run driverwin 200 python bench.py --gpus 1 --steps 20 --warmup 5 --cpu-seconds 10
+  run driverwin 200 python bench.py --gpus 1 --steps 20 --warmup 5 --full --cpu-seconds 10
   for c in $CONFIGS; do
     run bench_$c 300 python bench.py --config $c --steps ${BENCH_STEPS:-2000} --warmup ${BENCH_WARMUP:-200} --no-cpu-baseline
   done
