@@ -338,8 +338,8 @@ static int64_t queue_cap(int64_t N, int64_t E)
     return (blocks + kQShards - 1) / kQShards * E;
 }
 
-// The fused step's area of resetq (snake_kernels.hip k_step), after the two
-// queue sets: 64 logic-done counts (one line each), the groups' done and claim
+// The fused step's area of resetq (snake_kernels.hip k_step), after the
+// kQSets queue sets: 64 logic-done counts (one line each), the groups' done and claim
 // flags (at most N / 4 groups), the encodes' hand-off records (uint4 per env).
 int64_t fused_base(int64_t N)
 {
@@ -348,9 +348,6 @@ int64_t fused_base(int64_t N)
 }
 int64_t fused_words(int64_t N)
 {
-#ifdef SNAKE_NO_FUSED_AREA
-    return 0 * N;
-#endif
     return kQShards * kQSpread + 2 * round_up((N + 3) / 4, 4) + 4 * N;
 }
 

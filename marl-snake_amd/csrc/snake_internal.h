@@ -130,7 +130,7 @@ struct KCfg {
 
 int build_kcfg(const snake_cfg *c, int64_t num_envs, int64_t n_cand, KCfg *k);
 int layout_of(const snake_cfg *c, int64_t num_envs, snake_layout *out);
-// word offset in resetq of the fused step's area (after the two queue sets), and its words
+// word offset in resetq of the fused step's area (after the kQSets queue sets), and its words
 int64_t fused_base(int64_t num_envs);
 int64_t fused_words(int64_t num_envs);
 void set_error(const char *fmt, ...);

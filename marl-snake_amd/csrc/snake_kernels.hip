@@ -34,126 +34,27 @@
 #include <utility>
 
 #include "snake_internal.h"
+#include "snake_diag.h"
 
 constexpr int kResetWavesPerEU = 4;   // reset workers: 128 VGPRs (3 waves/SIMD measured slower)
 
 namespace snake {
 
-// Every launch goes through hipExtLaunchKernel: while a launch is timed
-// (TimedLaunch, snake_timing_enable) these are its start/stop events, which then
-// carry the dispatch's own begin/end timestamps -- no marker packets of their
-// own between the step's kernels (hipEventRecord pairs left 6 + 10.5 us gaps
-// around each timed step's k_logic / k_post in the kernel trace). Null: a
-// plain launch.
-thread_local hipEvent_t t_ev0 = nullptr, t_ev1 = nullptr;
-template <typename F, typename... Args>
-static inline void slaunch(F kernel, const dim3 &grid, const dim3 &block, uint32_t lds, hipStream_t s,
-                           Args... args)
-{
-    hipExtLaunchKernelGGL(kernel, grid, block, lds, s, t_ev0, t_ev1, 0u, args...);
-}
-
-__device__ unsigned long long g_resets_run;     // auto-resets run (snake_timing_read "resets")
-__device__ unsigned long long g_resets_timed;   // the same, while timing is enabled ("resets_timed")
-// (diagnostic counters, spread over 64 lines by block: one address taking a
-// device-scope atomic per job serialised thousands of them on the timed steps)
-constexpr int kDiagSlots = 64, kDiagSpread = 16;
-__device__ unsigned long long g_spawn_hits[kDiagSlots * kDiagSpread];   // auto-resets that found a ready record
-__device__ unsigned long long g_spawn_jobs[kDiagSlots * kDiagSpread];   // spawn-ahead jobs dequeued
-__device__ unsigned long long g_spawn_void[kDiagSlots * kDiagSpread];   // ready records voided by a fruit draw
-__device__ unsigned long long g_reset_part[kDiagSlots * kDiagSpread];   // auto-resets that found a partial record
-__device__ unsigned long long g_resp_slow[kDiagSlots * kDiagSpread];    // k_logic respawns on the full-wave path (no room)
-__device__ unsigned long long g_resp_slow2[kDiagSlots * kDiagSpread];   // ... (room, too few accepts among the prefetched raws)
-__device__ unsigned long long g_gate_shut[kDiagSlots * kDiagSpread];    // k_logic waves that found the background queue set busy
-__device__ unsigned long long g_draw_wait[kDiagSlots * kDiagSpread];    // resets that waited for a background job (DRAWING)
-__device__ unsigned long long g_draw_timeout[kDiagSlots * kDiagSpread]; // ... and gave up waiting (drew from the env's own state)
-#define DIAG_ADD(arr) atomicAdd(&(arr)[(blockIdx.x % kDiagSlots) * kDiagSpread], 1ull)
-#ifdef SNAKE_FUSE_DEBUG
-// (diagnostic build: range checks on the fused step's indices; a violation is
-// recorded -- site, value -- and the access skipped)
-__device__ unsigned long long g_fdbg[64];
-#define FDBG_BAD(site, val) (atomicAdd(&g_fdbg[2 * (site)], 1ull), atomicMax(&g_fdbg[2 * (site) + 1], (unsigned long long)(uint32_t)(val)), true)
-#define FDBG_MARK(site) do { if ((threadIdx.x & 63) == 0) atomicAdd(&g_fdbg[2 * (site)], 1ull); } while (0)
-#else
-#define FDBG_BAD(site, val) false
-#define FDBG_MARK(site) do {} while (0)
-#endif
-
-#ifdef SNAKE_STAMPS
-// Diagnostic build only (scripts/logic_stamps.py): s_memtime stamps of block
-// 0's wave at k_logic's phase boundaries, and s_memrealtime (100 MHz) at every
-// k_logic wave's start and end (its block index, up to kWaveTimes blocks).
-constexpr int kWaveTimes = 8192, kPostTimes = 40960;
-__device__ unsigned long long g_stamps[64];
-__device__ unsigned long long g_wavetime[2 * kWaveTimes];
-__device__ unsigned long long g_posttime[2 * kPostTimes];   // k_post: every block's start and end
-#define PTIME(end)                                                                 \
-    do {                                                                           \
-        __builtin_amdgcn_sched_barrier(0);                                         \
-        if ((threadIdx.x & 63) == 0 && blockIdx.x < kPostTimes)                    \
-            g_posttime[2 * blockIdx.x + (end)] = __builtin_amdgcn_s_memrealtime(); \
-        __builtin_amdgcn_sched_barrier(0);                                         \
-    } while (0)
-// (and every k_logic wave's s_memrealtime at each phase: g_wphase[wave][idx - 40])
-__device__ unsigned long long g_wphase[16 * kWaveTimes];
-#define LSTAMP(idx)                                                                \
-    do {                                                                           \
-        __builtin_amdgcn_sched_barrier(0);                                         \
-        if (blockIdx.x == 0) {                                                     \
-            unsigned long long _t = __builtin_amdgcn_s_memtime();                  \
-            if (threadIdx.x == 0) g_stamps[idx] = _t;                              \
-        }                                                                          \
-        const unsigned _w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);  \
-        if ((threadIdx.x & 63) == 0 && _w < kWaveTimes)                            \
-            g_wphase[16 * _w + (idx) - 40] = __builtin_amdgcn_s_memrealtime();     \
-        __builtin_amdgcn_sched_barrier(0);                                         \
-    } while (0)
-#define WTIME(end)                                                                 \
-    do {                                                                           \
-        __builtin_amdgcn_sched_barrier(0);                                         \
-        const unsigned _w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);  \
-        if ((threadIdx.x & 63) == 0 && _w < kWaveTimes)                            \
-            g_wavetime[2 * _w + (end)] = __builtin_amdgcn_s_memrealtime();         \
-        __builtin_amdgcn_sched_barrier(0);                                         \
-    } while (0)
-// every reset-worker item (scripts/post_items.py): worker | type << 32, start,
-// end (s_memrealtime), env; types 0 reset from a ready record, 1 from a partial
-// one, 2 without one, 3 queue-1 spawn-ahead job, 4 queue-2 job
-constexpr int kItems = 16384;
-__device__ unsigned g_nitems;
-__device__ unsigned long long g_items[4 * kItems];
-#define ITEM_T0() const unsigned long long _it0 = __builtin_amdgcn_s_memrealtime()
-#define ITEM_LOG(wid, type, e)                                                                      \
-    do {                                                                                           \
-        __builtin_amdgcn_sched_barrier(0);                                                         \
-        const unsigned long long _it1 = __builtin_amdgcn_s_memrealtime();                          \
-        if ((threadIdx.x & 63) == 0) {                                                             \
-            const unsigned _i = atomicAdd(&g_nitems, 1u);                                          \
-            if (_i < kItems) {                                                                     \
-                g_items[4 * _i] = (unsigned long long)(wid) | ((unsigned long long)(type) << 32);   \
-                g_items[4 * _i + 1] = _it0; g_items[4 * _i + 2] = _it1;                             \
-                g_items[4 * _i + 3] = (unsigned long long)(e);                                     \
-            }                                                                                      \
-        }                                                                                          \
-    } while (0)
-#else
-#define ITEM_T0() do {} while (0)
-#define ITEM_LOG(wid, type, e) do {} while (0)
-#define LSTAMP(idx) do {} while (0)
-#define WTIME(end) do {} while (0)
-#define PTIME(end) do {} while (0)
-#endif
-
 enum { C_EMPTY = 0, C_WALL = 1, C_FRUIT = 2, C_HEAD = 3, C_BODY = 4, C_TAIL = 5 };
 
 // The step and reset kernels take their arguments as one struct and read them
-// through kargs(): a pointer to the kernarg segment that the compiler cannot see
-// through (an empty asm), taken afresh at each phase or job. Every field is then
-// an s_load next to its use (the segment is constant, scalar-cached) instead of
-// a value held in an SGPR from the kernel's entry to its end: with the whole
-// KCfg, snake_state and snake_out live across a worker's job loop the compiler
-// spilled 230-300 SGPRs into VGPR lanes, 1 100-1 700 v_readlane reloads and
-// 128 VGPRs (profiles/r03_isa_counts.jsonl).
+// through kargs(kp): the kernarg-segment pointer passed through an empty asm
+// that the compiler cannot see through, afresh at each phase or job. Every field
+// is then an s_load next to its use (the segment is constant, scalar-cached)
+// instead of a value held in an SGPR from the kernel's entry to its end: with
+// the whole KCfg, snake_state and snake_out live across a worker's job loop the
+// compiler spilled 230-300 SGPRs into VGPR lanes, 1 100-1 700 v_readlane reloads
+// and 128 VGPRs (profiles/r03_isa_counts.jsonl).
+// The kernel takes the pointer as its first statement (kernel_args(): only
+// there does the builtin mean the running kernel's segment) and hands it down
+// as an argument, so a device function is right whether or not it is inlined;
+// __forceinline__ is for speed only. (encode_tbl_block<8, 64, *> is out of line
+// in the product build; it takes c, st, o by reference, which is as safe.)
 struct KArgs {
     KCfg c;
     snake_state st;
@@ -161,10 +62,16 @@ struct KArgs {
     const void *aux;   // k_logic: the actions; k_reset: the env mask
 };
 
-__device__ __forceinline__ const KArgs &kargs()
+typedef const __attribute__((address_space(4))) KArgs *KPtr;
+
+// only as the first statement of a __global__ kernel (tests/test_capi.py)
+__device__ __forceinline__ KPtr kernel_args()
 {
-    typedef const __attribute__((address_space(4))) KArgs KA4;
-    KA4 *p = (KA4 *)__builtin_amdgcn_kernarg_segment_ptr();   // (the first explicit argument is at offset 0)
+    return (KPtr)__builtin_amdgcn_kernarg_segment_ptr();   // (the first explicit argument is at offset 0)
+}
+
+__device__ __forceinline__ const KArgs &kargs(KPtr p)
+{
     __asm__ volatile("" : "+s"(p));
     return *(const KArgs *)p;
 }
@@ -1376,9 +1283,9 @@ struct LogicIn {
 };
 
 template <int MS, bool BG>
-__device__ __forceinline__ void logic_load(const int blk, LogicIn &in)
+__device__ __forceinline__ void logic_load(KPtr kp, const int blk, LogicIn &in)
 {
-    const KArgs &A = kargs();
+    const KArgs &A = kargs(kp);
     const KCfg &c = A.c;
     const snake_state &st = A.st;
     constexpr int G = MS, E = kWave / MS;
@@ -1414,10 +1321,10 @@ __device__ __forceinline__ void logic_load(const int blk, LogicIn &in)
 // auto-reset rewrites (records, statistics, ring words, crop centres, frame):
 // the two would race in two XCDs' L2s (k_step, below).
 template <int MS, bool BG, bool FU = false>
-__device__ __forceinline__ void logic_body(const int blk, const LogicIn &in)
+__device__ __forceinline__ void logic_body(KPtr kp, const int blk, const LogicIn &in)
 {
     LSTAMP(40);
-    const KArgs &A = kargs();
+    const KArgs &A = kargs(kp);
     const KCfg &c = A.c;
     const snake_state &st = A.st;
     const snake_out &o = A.o;
@@ -2071,12 +1978,13 @@ __device__ __forceinline__ void logic_body(const int blk, const LogicIn &in)
 template <int MS, int WPB, bool BG>
 __global__ void __launch_bounds__(64 * WPB) k_logic(const KArgs)
 {
+    const KPtr kp = kernel_args();
     WTIME(0);
     const int blk = (int)blockIdx.x * WPB + (int)(threadIdx.x >> 6);
-    if (blk * (kWave / MS) >= kargs().c.N) return;
+    if (blk * (kWave / MS) >= kargs(kp).c.N) return;
     LogicIn in;
-    logic_load<MS, BG>(blk, in);
-    logic_body<MS, BG>(blk, in);
+    logic_load<MS, BG>(kp, blk, in);
+    logic_body<MS, BG>(kp, blk, in);
     WTIME(1);
 }
 
@@ -2251,10 +2159,10 @@ __device__ __forceinline__ void encode_env(const KCfg &c, const snake_state &st,
 // global link tables; one path per instantiation.
 // wid = this worker (0 .. G-1): k_autoreset's block, or a block of k_post.
 template <int MS, bool RO, int JL>
-__device__ __forceinline__ void autoreset_worker(const int wid, const int G, uint8_t *lds)
+__device__ __forceinline__ void autoreset_worker(KPtr kp, const int wid, const int G, uint8_t *lds)
 {
     const int lane = threadIdx.x & (kWave - 1);
-    const KArgs &A = kargs();
+    const KArgs &A = kargs(kp);
     const KCfg &c = A.c;
     const snake_state &st = A.st;
     // the shard counts of the three queues, prefix-summed: queue index j lives
@@ -2294,15 +2202,13 @@ __device__ __forceinline__ void autoreset_worker(const int wid, const int G, uin
         // jobs; so is the lane index, or every lane mask derived from it -- the
         // MT word bounds, the scan steps -- would be held, spilled, for the whole
         // kernel instead of recomputed by one compare)
-        const KArgs &J = kargs();
+        const KArgs &J = kargs(kp);
         int lane = threadIdx.x & (kWave - 1);
         __asm__ volatile("" : "+v"(lane));
         if (idx < R) {
             __builtin_amdgcn_s_setprio(3);
             const int e = job_env(0, idx, incl);
-#ifdef SNAKE_FUSE_DEBUG
-            if ((e < 0 || e >= J.c.N) && FDBG_BAD(1, e)) { idx = 1 << 30; break; }
-#endif
+            FDBG_ENV_OR_STOP(1, e, J.c.N);
             ITEM_T0();
             WaveMT mt;
             uint32_t cellw;
@@ -2319,9 +2225,7 @@ __device__ __forceinline__ void autoreset_worker(const int wid, const int G, uin
             else __builtin_amdgcn_s_setprio(3);
             const int j = idx - R;
             const int e = j < U ? job_env(1, j, uincl) : job_env(2, j - U, nincl);
-#ifdef SNAKE_FUSE_DEBUG
-            if ((e < 0 || e >= J.c.N) && FDBG_BAD(2, e)) { idx = 1 << 30; break; }
-#endif
+            FDBG_ENV_OR_STOP(2, e, J.c.N);
             if (J.c.diag && lane == 0) DIAG_ADD(g_spawn_jobs);
             ITEM_T0();
             do_spawn<MS, JL>(J.c, J.st, e, lds, wid, lane);
@@ -2354,8 +2258,9 @@ __device__ __forceinline__ void autoreset_worker(const int wid, const int G, uin
 template <int MS, bool RO, int JL>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kResetWavesPerEU))) k_autoreset(const KArgs)
 {
+    const KPtr kp = kernel_args();
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    autoreset_worker<MS, RO, JL>((int)blockIdx.x, (int)gridDim.x, lds);
+    autoreset_worker<MS, RO, JL>(kp, (int)blockIdx.x, (int)gridDim.x, lds);
 }
 
 // Background spawn-ahead (KCfg.bg): the step's spawn-ahead jobs, run by
@@ -2367,7 +2272,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kResetW
 template <int MS>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kResetWavesPerEU))) k_spawn(const KArgs)
 {
-    const KArgs &A = kargs();
+    const KPtr kp = kernel_args();
+    const KArgs &A = kargs(kp);
     const KCfg &c = A.c;
     const snake_state &st = A.st;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -2399,7 +2305,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kResetW
         const int e = ent & ((1 << (32 - kQGenBits)) - 1);
         const uint32_t qgen = (uint32_t)ent >> (32 - kQGenBits);
         if (c.diag && lane == 0) DIAG_ADD(g_spawn_jobs);
-        const KArgs &J = kargs();
+        const KArgs &J = kargs(kp);
         do_spawn_bg<MS>(J.c, J.st, e, qgen, lds, lane);
         int v = 0;
         if (lane == 0) v = atomicAdd(&qc[(kQSpClaim + x) * kQSpread], 1);
@@ -2689,34 +2595,33 @@ __device__ void encode_tbl_block(const KCfg &c, const snake_state &st, const sna
 // count (launch_step); the counts grow by their shard's group count per step.
 // Every wait is bounded (kFuseWait): past it the wave carries on and the launch
 // counts the timeout ("fused_timeout"), the results are then undefined.
-__device__ unsigned long long g_fused_timeout[kDiagSlots * kDiagSpread];
 constexpr unsigned long long kFuseWait = 10000000ull;   // 100 ms of the 100 MHz clock
 constexpr unsigned long long kFuseHelp = 2000ull;       // 20 us: a waiting worker then claims unclaimed groups
 
-// (Everything here is inlined into k_step: kargs() reads the kernarg segment
-// pointer, which a called function does not have -- an out-of-line
-// fused_logic read its KCfg from garbage and faulted, round 6.)
-__device__ __forceinline__ bool fused_claim(const int g)
+// (Everything here takes k_step's kernarg pointer as an argument: round 6 read
+// the segment pointer inside these functions, which a called function does not
+// have -- an out-of-line fused_logic read its KCfg from garbage and faulted.)
+__device__ __forceinline__ bool fused_claim(KPtr kp, const int g)
 {
-    const KCfg &c = kargs().c;
-    uint32_t *claim = reinterpret_cast<uint32_t *>(kargs().st.resetq + c.fu_claim) + g;
+    const KCfg &c = kargs(kp).c;
+    uint32_t *claim = reinterpret_cast<uint32_t *>(kargs(kp).st.resetq + c.fu_claim) + g;
     int won = 0;
     if ((threadIdx.x & (kWave - 1)) == 0) won = atomicExch(claim, c.epoch) != c.epoch ? 1 : 0;
     return __shfl(won, 0) != 0;
 }
 
-__device__ __forceinline__ bool fused_group_done(const int g)
+__device__ __forceinline__ bool fused_group_done(KPtr kp, const int g)
 {
-    const KCfg &c = kargs().c;
-    const uint32_t *done = reinterpret_cast<const uint32_t *>(kargs().st.resetq + c.fu_done) + g;
+    const KCfg &c = kargs(kp).c;
+    const uint32_t *done = reinterpret_cast<const uint32_t *>(kargs(kp).st.resetq + c.fu_done) + g;
     return (uint32_t)__shfl((int)ld_sc1(done), 0) == c.epoch;
 }
 
 // an encode block's wait for its group's rules, which some wave has claimed
-__device__ __forceinline__ void fused_wait_group(const int g)
+__device__ __forceinline__ void fused_wait_group(KPtr kp, const int g)
 {
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    while (!fused_group_done(g)) {
+    while (!fused_group_done(kp, g)) {
         if (__builtin_amdgcn_s_memrealtime() - t0 > kFuseWait) {
             if ((threadIdx.x & (kWave - 1)) == 0) DIAG_ADD(g_fused_timeout);
             return;
@@ -2729,15 +2634,15 @@ __device__ __forceinline__ void fused_wait_group(const int g)
 // they are done (or the wait timed out), else a group it has just claimed and
 // must run -- once it has waited kFuseHelp, every group still unclaimed, from a
 // worker-specific start (`scan`: the next scan position, -1 before the first)
-__device__ __forceinline__ int fused_wait_all(const int wid, const unsigned long long t0, int &scan)
+__device__ __forceinline__ int fused_wait_all(KPtr kp, const int wid, const unsigned long long t0, int &scan)
 {
     const int lane = threadIdx.x & (kWave - 1);
     for (;;) {
-        const KCfg &c = kargs().c;
+        const KCfg &c = kargs(kp).c;
         const int nlg = c.nlg;
         // shard s (lane s) counts the groups g = s mod 64: (nlg - s + 63) / 64 of them per step
         const uint32_t ns = lane < nlg ? (uint32_t)((nlg - lane + kQShards - 1) / kQShards) : 0u;
-        const uint32_t v = ld_sc1(reinterpret_cast<const uint32_t *>(kargs().st.resetq + c.fu_ldone) + lane * kQSpread);
+        const uint32_t v = ld_sc1(reinterpret_cast<const uint32_t *>(kargs(kp).st.resetq + c.fu_ldone) + lane * kQSpread);
         if (__ballot(v != c.epoch * ns) == 0ull) return -1;
         const unsigned long long dt = __builtin_amdgcn_s_memrealtime() - t0;
         if (dt > kFuseWait) {
@@ -2748,15 +2653,15 @@ __device__ __forceinline__ int fused_wait_all(const int wid, const unsigned long
             if (scan < 0) scan = 0;
             for (; scan < nlg; scan += kWave) {
                 const int g = (wid * 61 + scan + lane) % nlg;
-                const KCfg &c2 = kargs().c;
-                const uint32_t cl = scan + lane < nlg ? ld_sc1(reinterpret_cast<const uint32_t *>(kargs().st.resetq + c2.fu_claim) + g)
+                const KCfg &c2 = kargs(kp).c;
+                const uint32_t cl = scan + lane < nlg ? ld_sc1(reinterpret_cast<const uint32_t *>(kargs(kp).st.resetq + c2.fu_claim) + g)
                                                       : c2.epoch;
                 unsigned long long m = __ballot(cl != c2.epoch);
                 while (m) {
                     const int L = __ffsll((long long)m) - 1;
                     m &= m - 1;
                     const int gg = __shfl(g, L);
-                    if (fused_claim(gg)) return gg;   // (the next call rescans this pass)
+                    if (fused_claim(kp, gg)) return gg;   // (the next call rescans this pass)
                 }
             }
         }
@@ -2769,11 +2674,12 @@ __device__ __forceinline__ int fused_wait_all(const int wid, const unsigned long
 template <int MS, int NPW, int JL>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) k_step(const KArgs)
 {
+    const KPtr kp = kernel_args();
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     PTIME(0);
     const int b = (int)blockIdx.x;
-    const int nlg = kargs().c.nlg, G = kargs().c.reset_slots;
-    const int roles = kargs().c.fu_roles;   // (snake_debug_set "fuse_roles": 7 = all)
+    const int nlg = kargs(kp).c.nlg, G = kargs(kp).c.reset_slots;
+    const int roles = kargs(kp).c.fu_roles;   // (snake_debug_set "fuse_roles": 7 = all)
     const int role = b < nlg ? 0 : (b < nlg + G ? 1 : 2);   // rules, reset worker, encodes
     if (!(roles & (1 << role))) return;
     const int j = b - nlg - G;   // (encodes: envs 4j .. 4j + 3, all of logic group 4j / (64 / MS))
@@ -2784,16 +2690,16 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) k_
     for (int it = 0;; it++) {
         int grp = -1;
         if (role == 0) {
-            if (it == 0 && fused_claim(b)) grp = b;
+            if (it == 0 && fused_claim(kp, b)) grp = b;
         } else if (role == 2) {
-            if (it == 0 && !fused_group_done(eg) && fused_claim(eg)) grp = eg;
+            if (it == 0 && !fused_group_done(kp, eg) && fused_claim(kp, eg)) grp = eg;
         } else {
-            grp = fused_wait_all(b - nlg, t0, scan);
+            grp = fused_wait_all(kp, b - nlg, t0, scan);
         }
         if (grp < 0) break;
         LogicIn in;
-        logic_load<MS, false>(grp, in);
-        logic_body<MS, false, true>(grp, in);
+        logic_load<MS, false>(kp, grp, in);
+        logic_body<MS, false, true>(kp, grp, in);
         FDBG_MARK(3);
     }
     if (role == 0) { PTIME(1); return; }
@@ -2802,15 +2708,15 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) k_
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
         FDBG_MARK(4);
-        autoreset_worker<4, false, JL>(b - nlg, G, lds);
+        autoreset_worker<4, false, JL>(kp, b - nlg, G, lds);
         FDBG_MARK(5);
         PTIME(1);
         return;
     }
-    if (4 * j >= kargs().c.N && FDBG_BAD(6, j)) return;
-    fused_wait_group(eg);
+    if (4 * j >= kargs(kp).c.N && FDBG_BAD(6, j)) return;
+    fused_wait_group(kp, eg);
     FDBG_MARK(7);
-    const KArgs &A = kargs();
+    const KArgs &A = kargs(kp);
     encode_tbl_block<NPW, kWave, true>(A.c, A.st, A.o, j);
     PTIME(1);
 }
@@ -2819,19 +2725,20 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) k_
 template <int MS, int NPF, bool RO, int JL>
 __global__ void __launch_bounds__(64) k_post(const KArgs)
 {
+    const KPtr kp = kernel_args();
     PTIME(0);
-    const int G = kargs().c.reset_slots, b = (int)blockIdx.x;
+    const int G = kargs(kp).c.reset_slots, b = (int)blockIdx.x;
     if (b < G) {
         extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
 #ifdef SNAKE_DIAG_ENC2   // (diagnostic: the second, encode-only launch, see launch_step)
-        if (kargs().aux) return;
+        if (kargs(kp).aux) return;
 #endif
-        autoreset_worker<MS, RO, JL>(b, G, lds);
+        autoreset_worker<MS, RO, JL>(kp, b, G, lds);
     } else {
 #ifdef SNAKE_DIAG_NO_ENCODE   // (diagnostic build: instruction counts without the encodes)
         return;
 #endif
-        const KArgs &A = kargs();
+        const KArgs &A = kargs(kp);
         if constexpr (NPF == 0) encode_one(A.c, A.st, A.o, b - G);
         else if constexpr (NPF < 0) encode_tbl_block<-NPF>(A.c, A.st, A.o, b - G);
         else encode_multi<NPF>(A.c, A.st, A.o, b - G);
@@ -2921,14 +2828,15 @@ __device__ __forceinline__ void encode_lean_block(const KCfg &c, const snake_sta
 template <int MS, bool RO, bool TBL>
 __global__ void __launch_bounds__(256) k_post_lean(const KArgs)
 {
+    const KPtr kp = kernel_args();
     PTIME(0);
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const int G = kargs().c.reset_slots, GB = (G + 3) >> 2, b = (int)blockIdx.x;
+    const int G = kargs(kp).c.reset_slots, GB = (G + 3) >> 2, b = (int)blockIdx.x;
     if (b < GB) {
         const int wave = (int)(threadIdx.x >> 6), wid = 4 * b + wave;
-        if (wid < G) autoreset_worker<MS, RO, 0>(wid, G, lds + wave * kargs().c.lds_worker);
+        if (wid < G) autoreset_worker<MS, RO, 0>(kp, wid, G, lds + wave * kargs(kp).c.lds_worker);
     } else {
-        const KArgs &A = kargs();
+        const KArgs &A = kargs(kp);
         if constexpr (TBL) encode_tbl_block<8, 256>(A.c, A.st, A.o, b - GB);
         else encode_lean_block<8, 256>(A.c, A.st, A.o, b - GB);
     }
@@ -2938,12 +2846,13 @@ __global__ void __launch_bounds__(256) k_post_lean(const KArgs)
 template <int MS, int JL>
 __global__ void __launch_bounds__(64) k_reset(const KArgs)
 {
+    const KPtr kp = kernel_args();
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int lane = threadIdx.x;
     // one env per block with the link table in LDS (JL), else reset_slots
     // workers striding over the envs, each with its own global link table
-    for (int e = blockIdx.x; e < kargs().c.N; e += gridDim.x) {
-        const KArgs &J = kargs();
+    for (int e = blockIdx.x; e < kargs(kp).c.N; e += gridDim.x) {
+        const KArgs &J = kargs(kp);
         const uint8_t *mask = (const uint8_t *)J.aux;
         if (mask && !mask[e]) continue;
         WaveMT mt;
@@ -2951,7 +2860,7 @@ __global__ void __launch_bounds__(64) k_reset(const KArgs)
         const int spst = load_reset_mt(J.c, J.st, e, mt, lane, true, cellw);
         do_reset<MS, JL>(J.c, J.st, J.o, e, mt, lds, blockIdx.x, spst, cellw, lane);
         // with spawn-ahead on, the next reset's poses are drawn now, off the step
-        const KArgs &J2 = kargs();
+        const KArgs &J2 = kargs(kp);
         if (J2.c.spawn_thr >= 0) spawn_after_reset<MS, JL>(J2.c, J2.st, e, mt, lds, blockIdx.x, lane);
     }
 }
@@ -3016,653 +2925,9 @@ __global__ void k_render(const KCfg c, const snake_state st, const RenderPal pal
     }
 }
 
-// ------------------------------------------------------------- kernel timing
-// Profiling aid (snake_timing_enable / snake_timing_read): pairs of timing events
-// around each launch, resolved when read. Event objects are pooled.
-namespace {
-struct TimingRec {
-    const char *name;
-    hipEvent_t a, b;
-};
-std::mutex g_tmu;
-bool g_timing = false;
-int g_draw_wait_ticks = 200000;   // KCfg.draw_wait (snake_debug_set "draw_wait_ticks")
-int g_spawn_delay_ticks = 0;      // KCfg.spawn_delay (snake_debug_set "spawn_delay_ticks")
-int g_fuse_roles = 7;             // KCfg.fu_roles (snake_debug_set "fuse_roles", diagnostics)
-#ifndef SNAKE_FUSED
-#define SNAKE_FUSED 0
-#endif
-int g_fused = SNAKE_FUSED;        // the fused step where KCfg.fused allows it (snake_debug_set "fused")
-std::vector<TimingRec> g_pending;
-std::vector<hipEvent_t> g_pool;
-std::map<std::string, std::pair<double, int64_t>> g_done;
-
-hipEvent_t pooled_event()
-{
-    if (!g_pool.empty()) {
-        hipEvent_t ev = g_pool.back();
-        g_pool.pop_back();
-        return ev;
-    }
-    hipEvent_t ev = nullptr;
-    // timing only: no system-scope fence (cache write-back and invalidate) when
-    // the event completes, which would delay the next kernel
-    if (hipEventCreateWithFlags(&ev, hipEventDisableSystemFence) != hipSuccess) return nullptr;
-    return ev;
-}
-}  // namespace
-
-// Times the one launch (slaunch) made between its construction and close():
-// the pair of pooled events rides on that launch (no-ops when timing is off).
-struct TimedLaunch {
-    const char *name;
-    hipEvent_t a = nullptr, b = nullptr;
-    TimedLaunch(const char *n, hipStream_t) : name(n)
-    {
-        std::lock_guard<std::mutex> g(g_tmu);
-        if (!g_timing) return;
-        a = pooled_event();
-        b = a ? pooled_event() : nullptr;
-        if (!b) {
-            if (a) g_pool.push_back(a);
-            a = nullptr;
-            return;
-        }
-        t_ev0 = a;
-        t_ev1 = b;
-    }
-    void close()
-    {
-        if (!a) return;
-        t_ev0 = t_ev1 = nullptr;
-        std::lock_guard<std::mutex> g(g_tmu);
-        // (a failed launch records neither: check_launch reports it, the pair
-        // goes back to the pool)
-        if (hipPeekAtLastError() == hipSuccess) g_pending.push_back({name, a, b});
-        else {
-            g_pool.push_back(a);
-            g_pool.push_back(b);
-        }
-        a = nullptr;
-    }
-    ~TimedLaunch() { close(); }
-};
-
-// Every launch runs with the caller stream's device current: the side stream and
-// events are created on it, and a SnakeVecEnv on cuda:1 works whatever device the
-// calling thread has current (restored on return).
-struct DeviceGuard {
-    int dev = -1, prev = -1;
-    explicit DeviceGuard(hipStream_t s)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) { set_error("hipGetDevice failed"); return; }
-        if (s == nullptr) { dev = prev; return; }
-        if (hipStreamGetDevice(s, &dev) != hipSuccess) {
-            set_error("hipStreamGetDevice failed");
-            dev = -1;
-            return;
-        }
-        if (dev != prev && hipSetDevice(dev) != hipSuccess) {
-            set_error("hipSetDevice(%d) failed", dev);
-            dev = -1;
-        }
-    }
-    ~DeviceGuard()
-    {
-        if (prev >= 0 && dev >= 0 && dev != prev) (void)hipSetDevice(prev);
-    }
-};
-
-// ---------------------------------------------------------------- launchers
-static int check_launch(const char *what)
-{
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        set_error("%s launch failed: %s", what, hipGetErrorString(err));
-        return SNAKE_E_LAUNCH;
-    }
-    return SNAKE_OK;
-}
-
-// The background stream's events only order kernels of one device: no
-// system-scope fence (that would write the L2s back for a host that never looks).
-constexpr unsigned kJoinFlags = hipEventDisableTiming | hipEventDisableSystemFence;
-
-// Background spawn-ahead (KCfg.bg) per state (keyed by its env records): the
-// stream k_spawn runs on, the event the caller's stream records after k_logic
-// (k_spawn's start), the event recorded after the last k_spawn of each queue
-// set, the step counter whose parity picks the queue set. Created by the
-// state's first step, destroyed by snake_release.
-// One background stream per queue set (round 5): a set's k_spawn only waits for
-// that set's previous one, so consecutive steps' spawn kernels may overlap --
-// with one stream they queued behind each other (a 40x40 job takes about a
-// step) and k_logic found its set's previous kernel unfinished in ~21 % of
-// cfg5's steps, queued nothing, and the next step's resets drew inline.
-constexpr int kBgStreams = 2;
-struct BgCtx {
-    // (two streams for the four queue sets, set p on stream p % 2: every
-    // stream takes one of the process's hardware queues -- GPU_MAX_HW_QUEUES,
-    // 4 by default -- and with four background streams the caller's stream
-    // shared one with a spawn kernel: cfg5 0.0811 -> 0.0980 ms, round 6)
-    hipStream_t x[kBgStreams] = {};
-    hipEvent_t fork = nullptr;
-    hipEvent_t done[kQSets] = {};
-    uint64_t steps = 0;
-    bool pending[kQSets] = {};
-    uint32_t launched[kQSets] = {};   // k_spawn launches per queue set (KCfg.spawn_gate)
-};
-static std::mutex g_bgmu;
-static std::map<const void *, BgCtx> g_bg;
-// The fused step's per-state epoch (k_step): the number of k_step launches of
-// the state so far; its flag area is zeroed on the state's first fused step.
-static std::map<const void *, uint32_t> g_fu;
-
-static void destroy_bg(BgCtx &c)
-{
-    for (hipStream_t x : c.x)
-        if (x) (void)hipStreamSynchronize(x);   // (its last k_spawn)
-    if (c.fork) (void)hipEventDestroy(c.fork);
-    for (hipEvent_t ev : c.done)
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipStream_t x : c.x)
-        if (x) (void)hipStreamDestroy(x);
-    c = BgCtx();
-}
-
-static BgCtx *bg_ctx(const snake_state &st, bool create)
-{
-    std::lock_guard<std::mutex> g(g_bgmu);
-    auto it = g_bg.find(st.env);
-    if (it != g_bg.end()) return &it->second;
-    if (!create) return nullptr;
-    BgCtx c;
-    bool ok = true;
-    for (int p = 0; p < kBgStreams && ok; p++)
-        ok = hipStreamCreateWithFlags(&c.x[p], hipStreamNonBlocking) == hipSuccess;
-    for (int p = 0; p < kQSets && ok; p++)
-        ok = hipEventCreateWithFlags(&c.done[p], kJoinFlags) == hipSuccess;
-    // (the fork event rides on k_logic's dispatch as its stop event, like the
-    // timing events: a timing-capable event without the system fence)
-    if (!ok || hipEventCreateWithFlags(&c.fork, hipEventDisableSystemFence) != hipSuccess) {
-        destroy_bg(c);
-        set_error("background stream / event creation failed");
-        return nullptr;
-    }
-    return &g_bg.emplace(st.env, c).first->second;   // (std::map: the address stays valid)
-}
-
-// `stream` waits for the state's last background spawn kernel (if any).
-int wait_background(const snake_state &st, void *stream)
-{
-    BgCtx *b = bg_ctx(st, false);
-    if (!b) return SNAKE_OK;
-    for (int p = 0; p < kQSets; p++)
-        if (b->pending[p] && hipStreamWaitEvent((hipStream_t)stream, b->done[p], 0) != hipSuccess) {
-            set_error("waiting for the background spawn kernel failed");
-            return SNAKE_E_LAUNCH;
-        }
-    return SNAKE_OK;
-}
-
-// The state's background context (snake_release): its last spawn kernel
-// waited for on the host, its stream and events destroyed, the entry erased,
-// so an allocation that later reuses the same env address starts afresh.
-int release_background(const snake_state &st)
-{
-    BgCtx c;
-    {
-        std::lock_guard<std::mutex> g(g_bgmu);
-        g_fu.erase(st.env);
-        auto it = g_bg.find(st.env);
-        if (it == g_bg.end()) return SNAKE_OK;
-        c = it->second;
-        g_bg.erase(it);
-    }
-    DeviceGuard dg(c.x[0]);   // (the streams' device current while they are destroyed)
-    destroy_bg(c);
-    return dg.dev < 0 ? SNAKE_E_LAUNCH : SNAKE_OK;
-}
-
-int launch_seed(const KCfg &k, const snake_state &st, uint32_t base_seed, int64_t env_offset,
-                void *stream)
-{
-    const int threads = 256, blocks = (k.N + threads - 1) / threads;
-    DeviceGuard dg((hipStream_t)stream);
-    if (dg.dev < 0) return SNAKE_E_LAUNCH;
-    if (int rc = wait_background(st, stream)) return rc;
-    slaunch(k_seed, dim3(blocks), dim3(threads), 0, (hipStream_t)stream, k, st,
-                       base_seed, (long long)env_offset);
-    return check_launch("k_seed");
-}
-
-int launch_render(const KCfg &k, const snake_state &st, const uint8_t *palette, uint8_t *rgb,
-                  void *stream)
-{
-    RenderPal pal;
-    memcpy(pal.rgb, palette, sizeof(pal.rgb));
-    DeviceGuard dg((hipStream_t)stream);
-    if (dg.dev < 0) return SNAKE_E_LAUNCH;
-    const long long quads = ((long long)k.N * k.HW + 3) / 4;
-    const int threads = 256;
-    const long long blocks = (quads + threads - 1) / threads;
-    slaunch(k_render, dim3((unsigned)blocks), dim3(threads), 0, (hipStream_t)stream, k, st,
-                       pal, rgb);
-    return check_launch("k_render");
-}
-
-int launch_reset(const KCfg &k, const snake_state &st, const uint8_t *mask, const snake_out &o,
-                 void *stream)
-{
-    const dim3 grid(k.link_in_lds ? k.N : k.reset_slots), block(kWave);
-    DeviceGuard dg((hipStream_t)stream);
-    if (dg.dev < 0) return SNAKE_E_LAUNCH;
-    if (int rc = wait_background(st, stream)) return rc;
-    TimedLaunch tl("k_reset", (hipStream_t)stream);
-    const KArgs a{k, st, o, mask};
-    const hipStream_t s = (hipStream_t)stream;
-    if (k.link32) {
-        if (k.S <= 4) slaunch((k_reset<4, 2>), grid, block, k.lds_bytes, s, a);
-        else if (k.S <= 8) slaunch((k_reset<8, 2>), grid, block, k.lds_bytes, s, a);
-        else slaunch((k_reset<16, 2>), grid, block, k.lds_bytes, s, a);
-    } else if (k.link_in_lds) {
-        if (k.S <= 4) slaunch((k_reset<4, 1>), grid, block, k.lds_bytes, s, a);
-        else if (k.S <= 8) slaunch((k_reset<8, 1>), grid, block, k.lds_bytes, s, a);
-        else slaunch((k_reset<16, 1>), grid, block, k.lds_bytes, s, a);
-    } else {
-        if (k.S <= 4) slaunch((k_reset<4, 0>), grid, block, k.lds_bytes, s, a);
-        else if (k.S <= 8) slaunch((k_reset<8, 0>), grid, block, k.lds_bytes, s, a);
-        else slaunch((k_reset<16, 0>), grid, block, k.lds_bytes, s, a);
-    }
-    tl.close();
-    return check_launch("k_reset");
-}
-
-// k_post<MS(S), NPF, RO, JL> (see k_post)
-template <int MS, bool RO, int JL>
-static void launch_post(const KCfg &k, const KArgs &a, int npf, dim3 grid, int lds, hipStream_t s)
-{
-    const dim3 block(kWave);
-    if (npf == 0) slaunch((k_post<MS, 0, RO, JL>), grid, block, lds, s, a);
-    else if (npf == -2) slaunch((k_post<MS, -2, RO, JL>), grid, block, lds, s, a);
-    else if (npf == -8) slaunch((k_post<MS, -8, RO, JL>), grid, block, lds, s, a);
-    else if (npf == 1) slaunch((k_post<MS, 1, RO, JL>), grid, block, lds, s, a);
-    else if (npf == 2) slaunch((k_post<MS, 2, RO, JL>), grid, block, lds, s, a);
-    else slaunch((k_post<MS, 8, RO, JL>), grid, block, lds, s, a);
-}
-
-template <bool RO, int JL>
-static void launch_post_s(const KCfg &k, const KArgs &a, int npf, dim3 grid, int lds, hipStream_t s)
-{
-    if (k.S <= 4) launch_post<4, RO, JL>(k, a, npf, grid, lds, s);
-    else if (k.S <= 8) launch_post<8, RO, JL>(k, a, npf, grid, lds, s);
-    else launch_post<16, RO, JL>(k, a, npf, grid, lds, s);
-}
-
-// k_autoreset<MS(S), RO, JL(k.link_in_lds)> (every-step mode: resets only)
-static void launch_autoreset_ro(const KCfg &k, const KArgs &a, dim3 grid, hipStream_t s)
-{
-    const dim3 block(kWave);
-    if (k.link_in_lds) {
-        if (k.S <= 4) slaunch((k_autoreset<4, true, 1>), grid, block, k.lds_bytes, s, a);
-        else if (k.S <= 8) slaunch((k_autoreset<8, true, 1>), grid, block, k.lds_bytes, s, a);
-        else slaunch((k_autoreset<16, true, 1>), grid, block, k.lds_bytes, s, a);
-    } else {
-        if (k.S <= 4) slaunch((k_autoreset<4, true, 0>), grid, block, k.lds_bytes, s, a);
-        else if (k.S <= 8) slaunch((k_autoreset<8, true, 0>), grid, block, k.lds_bytes, s, a);
-        else slaunch((k_autoreset<16, true, 0>), grid, block, k.lds_bytes, s, a);
-    }
-}
-
-// snake_step: k_logic, then (all-done auto-reset) the shared phase as ONE launch
-// on the caller's stream -- k_post, or k_post_lean on boards with four-wave lean
-// encodes -- with, on background spawn-ahead boards, k_spawn forked onto the
-// state's background stream after k_logic and not joined.
-int launch_step(const KCfg &k0, const snake_state &st, const int8_t *actions, const snake_out &o,
-                void *stream)
-{
-    KCfg k = k0;
-    k.diag = g_timing ? 1 : 0;
-    k.draw_wait = g_draw_wait_ticks;
-    k.spawn_delay = g_spawn_delay_ticks;
-    k.fu_roles = g_fuse_roles;
-    const hipStream_t sm = (hipStream_t)stream;
-    DeviceGuard dg(sm);
-    if (dg.dev < 0) return SNAKE_E_LAUNCH;
-    const int ms = k.logic_ms, epw = kWave / ms;   // envs per k_logic wave
-    const int lds_logic = k.lds_logic;
-    const dim3 g1(k.N), gl((k.N + epw - 1) / epw), gr(k.reset_slots), block(kWave);
-    // everything that can fail before k_logic fills this step's queue set
-    BgCtx *bgc = nullptr;
-    if (k.bg) {   // background spawn-ahead: this step's queue set; k_logic queues
-                  // spawn-ahead jobs into it only if the spawn kernels launched on
-                  // it so far have finished (kQSpGen), the stream never waits
-                  // (the wait cost cfg5 0.1026 -> 0.1136 ms per step)
-        if (!(bgc = bg_ctx(st, true))) return SNAKE_E_LAUNCH;
-        k.qpar = (int)(bgc->steps % kQSets);
-        k.spawn_gate = bgc->launched[k.qpar];
-    }
-    if (k.fused && g_fused) {   // the whole step as one launch (k_step)
-        uint32_t ep;
-        bool fresh = false;
-        {
-            std::lock_guard<std::mutex> g(g_bgmu);
-            auto it = g_fu.find(st.env);
-            if (it == g_fu.end()) { it = g_fu.emplace(st.env, 0u).first; fresh = true; }
-            ep = it->second;
-        }
-        if (fresh && hipMemsetAsync(st.resetq + k.fu_ldone, 0, sizeof(int) * fused_words(k.N), sm) != hipSuccess) {
-            set_error("zeroing the fused step's flags failed");
-            return SNAKE_E_LAUNCH;
-        }
-        k.epoch = ep + 1;
-        const int npw = (k.fs * k.HW / 4 + kWave - 1) / kWave;
-        const dim3 gf(k.nlg + k.reset_slots + (k.N + 3) / 4), bf(kWave);
-        const int lds_f = std::max(k.lds_logic, std::max(k.lds_bytes, k.lds_tbl_bytes));
-        const KArgs fa{k, st, o, actions};
-        TimedLaunch tf("k_step", sm);
-        auto go = [&](auto msc, auto npwc) {
-            constexpr int MS = decltype(msc)::value, NPW = decltype(npwc)::value;
-            if (k.link32) slaunch((k_step<MS, NPW, 2>), gf, bf, lds_f, sm, fa);
-            else slaunch((k_step<MS, NPW, 1>), gf, bf, lds_f, sm, fa);
-        };
-        using I2 = std::integral_constant<int, 2>;
-        using I4 = std::integral_constant<int, 4>;
-        using I8 = std::integral_constant<int, 8>;
-        if (ms == 4) { if (npw <= 2) go(I4{}, I2{}); else go(I4{}, I8{}); }
-        else { if (npw <= 2) go(I8{}, I2{}); else go(I8{}, I8{}); }
-        tf.close();
-        if (int rc2 = check_launch("k_step")) return rc2;
-        std::lock_guard<std::mutex> g(g_bgmu);
-        g_fu[st.env] = ep + 1;
-        return SNAKE_OK;
-    }
-    TimedLaunch t1("k_logic", sm);
-    // Background spawn-ahead: the fork onto the background stream is k_logic's
-    // own dispatch -- its stop event (the timing event when the launch is timed)
-    // -- not an event record of its own on the caller's stream: that marker
-    // packet stood between k_logic and k_post, 5.3 us of idle GPU per step at
-    // 8 192 envs (round 6 kernel trace).
-    hipEvent_t fork_ev = nullptr;
-    if (bgc) {
-        if (!t_ev1) t_ev1 = bgc->fork;
-        fork_ev = t_ev1;
-    }
-    const KArgs la{k, st, o, actions};
-    // four waves (groups) per workgroup where their LDS fits (KCfg.logic_wpb):
-    // k_logic cfg4 20.4 -> 19.4 us, cfg5 21.9 -> 21.1 against one (round 4)
-    auto launch_logic = [&](auto wpb) {
-        constexpr int WPB = decltype(wpb)::value;
-        const dim3 glb((gl.x + WPB - 1) / WPB), blb(kWave * WPB);
-        if (k.bg) {
-            if (ms == 4) slaunch((k_logic<4, WPB, true>), glb, blb, WPB * lds_logic, sm, la);
-            else if (ms == 8) slaunch((k_logic<8, WPB, true>), glb, blb, WPB * lds_logic, sm, la);
-            else slaunch((k_logic<16, WPB, true>), glb, blb, WPB * lds_logic, sm, la);
-        } else {
-            if (ms == 4) slaunch((k_logic<4, WPB, false>), glb, blb, WPB * lds_logic, sm, la);
-            else if (ms == 8) slaunch((k_logic<8, WPB, false>), glb, blb, WPB * lds_logic, sm, la);
-            else slaunch((k_logic<16, WPB, false>), glb, blb, WPB * lds_logic, sm, la);
-        }
-    };
-    if (k.logic_wpb == 4) launch_logic(std::integral_constant<int, 4>{});
-    else launch_logic(std::integral_constant<int, 1>{});
-    if (bgc && fork_ev == bgc->fork) t_ev1 = nullptr;
-    t1.close();
-    int rc = check_launch("k_logic");
-    if (rc) return rc;
-    // From here on k_logic has filled this step's queue set: a failure zeroes
-    // its counters, so the next step does not run this step's queues. Once
-    // k_spawn is launched it owns the set's spawn counters (it reads them and
-    // re-zeroes them at its end): only the reset counters are zeroed
-    // then -- queue 0's shard counts and the claim / done counters.
-    bool spawn_launched = false;
-    auto fail = [&](int r) {
-        int *qc = st.resetq + (int64_t)k.qpar * (kNumQ * kQShards * k.q_cap + kQCounters) +
-                  kNumQ * kQShards * k.q_cap;
-        if (!spawn_launched) {
-            // (ordered after the set's previous k_spawn, which may still use its
-            // spawn and claim counters on its background stream)
-            if (bgc && bgc->pending[k.qpar]) (void)hipStreamWaitEvent(sm, bgc->done[k.qpar], 0);
-            (void)hipMemsetAsync(qc, 0, sizeof(int) * kQSpGen * kQSpread, sm);   // (not the finished count)
-        } else {
-            (void)hipMemsetAsync(qc, 0, sizeof(int) * kQShards * kQSpread, sm);
-            (void)hipMemsetAsync(qc + kQClaim * kQSpread, 0, sizeof(int) * (kQDone + 1 - kQClaim) * kQSpread, sm);
-        }
-        return r;
-    };
-    const KArgs a{k, st, o, nullptr};
-    if (k.autoreset == 2) {   // every env resets (the resets write the obs), then the
-                              // encodes of the envs rejected for an invalid action
-        TimedLaunch t2("k_autoreset", sm);
-        launch_autoreset_ro(k, a, gr, sm);
-        t2.close();
-        if ((rc = check_launch("k_autoreset"))) return fail(rc);
-        TimedLaunch t3("k_encode", sm);
-        slaunch(k_encode, g1, block, k.lds_obs_bytes, sm, k, st, o);
-        t3.close();
-        return check_launch("k_encode");
-    }
-    if (!k.autoreset) {
-        TimedLaunch t3("k_encode", sm);
-        slaunch(k_encode, g1, block, k.lds_obs_bytes, sm, k, st, o);
-        t3.close();
-        return check_launch("k_encode");
-    }
-    if (bgc) {
-        // this step's spawn kernel on the background stream once k_logic has
-        // passed (its dispatch's stop event, above); not joined (k_logic two
-        // steps later only queues into the set once it has finished)
-        hipStream_t bx = bgc->x[k.qpar % kBgStreams];
-        if (hipStreamWaitEvent(bx, fork_ev, 0) != hipSuccess) {
-            set_error("fork to the background stream failed");
-            return fail(SNAKE_E_LAUNCH);
-        }
-        KCfg ks = k;
-        ks.lds_link = 0;   // (only the draw record)
-        const int lds_sp = (int)(((int64_t)2 * (k.n_cand + kWave) + 15) / 16 * 16);
-        const dim3 gs(k.spawn_slots);
-        TimedLaunch t4("k_spawn", bx);
-        const KArgs sa{ks, st, o, nullptr};
-        if (k.S <= 4) slaunch(k_spawn<4>, gs, block, lds_sp, bx, sa);
-        else if (k.S <= 8) slaunch(k_spawn<8>, gs, block, lds_sp, bx, sa);
-        else slaunch(k_spawn<16>, gs, block, lds_sp, bx, sa);
-        t4.close();
-        if ((rc = check_launch("k_spawn"))) return fail(rc);
-        // (counted as soon as it is launched: its last worker adds one to the
-        // set's finished count whatever fails after this point)
-        spawn_launched = true;
-        bgc->launched[k.qpar]++;
-        bgc->steps++;
-        if (hipEventRecord(bgc->done[k.qpar], bx) != hipSuccess) {
-            // (pending / done[] would not cover this k_spawn, which writes
-            // records, env word 4 and the set's counters: wait for it here so
-            // that snake_sync and the next steps need not)
-            (void)hipStreamSynchronize(bx);
-            set_error("background spawn event failed");
-            return fail(SNAKE_E_LAUNCH);
-        }
-        bgc->pending[k.qpar] = true;
-    }
-    TimedLaunch t2("k_post", sm);
-    if (k.lean) {
-        // four workers per workgroup, then the four-wave lean encodes
-        const dim3 gp((k.reset_slots + 3) / 4 + (k.N + k.enc_per_wave - 1) / k.enc_per_wave);
-        const int lds_p = std::max(4 * k.lds_worker, k.tbl ? k.lds_tbl_bytes : k.lds_lean_bytes);
-        if (k.tbl) {   // (the table encode in four-wave workgroups)
-            if (k.bg) {
-                if (k.S <= 4) slaunch((k_post_lean<4, true, true>), gp, dim3(256), lds_p, sm, a);
-                else if (k.S <= 8) slaunch((k_post_lean<8, true, true>), gp, dim3(256), lds_p, sm, a);
-                else slaunch((k_post_lean<16, true, true>), gp, dim3(256), lds_p, sm, a);
-            } else {
-                if (k.S <= 4) slaunch((k_post_lean<4, false, true>), gp, dim3(256), lds_p, sm, a);
-                else if (k.S <= 8) slaunch((k_post_lean<8, false, true>), gp, dim3(256), lds_p, sm, a);
-                else slaunch((k_post_lean<16, false, true>), gp, dim3(256), lds_p, sm, a);
-            }
-        } else if (k.bg) {
-            if (k.S <= 4) slaunch((k_post_lean<4, true, false>), gp, dim3(256), lds_p, sm, a);
-            else if (k.S <= 8) slaunch((k_post_lean<8, true, false>), gp, dim3(256), lds_p, sm, a);
-            else slaunch((k_post_lean<16, true, false>), gp, dim3(256), lds_p, sm, a);
-        } else {
-            if (k.S <= 4) slaunch((k_post_lean<4, false, false>), gp, dim3(256), lds_p, sm, a);
-            else if (k.S <= 8) slaunch((k_post_lean<8, false, false>), gp, dim3(256), lds_p, sm, a);
-            else slaunch((k_post_lean<16, false, false>), gp, dim3(256), lds_p, sm, a);
-        }
-    } else {
-        // the workers, then the encodes: NPF = 16-byte ring chunks per lane the
-        // two-env encode keeps in flight, 0 = one env per block
-        const int epw2 = k.enc_per_wave, n16 = k.ring_bytes >> 4;
-        const int npw = (k.fs * k.HW / 4 + kWave - 1) / kWave;   // frame dwords per lane (table encode)
-        const int npf = k.tbl ? (npw <= 2 ? -2 : -8)
-                              : (epw2 <= 1 ? 0 : (n16 <= kWave ? 1 : (n16 <= 2 * kWave ? 2 : 8)));
-        const int enc_blocks = npf == 0 ? k.N : (k.N + epw2 - 1) / epw2;
-        const dim3 gp(k.reset_slots + enc_blocks);
-        const int lds_p = std::max(k.lds_bytes, k.tbl ? k.lds_tbl_bytes : k.lds_obs_bytes);
-        if (k.bg) launch_post_s<true, 1>(k, a, npf, gp, lds_p, sm);   // (background boards keep the LDS record)
-        else if (k.link32) launch_post_s<false, 2>(k, a, npf, gp, lds_p, sm);
-        else if (k.link_in_lds) launch_post_s<false, 1>(k, a, npf, gp, lds_p, sm);
-        else launch_post_s<false, 0>(k, a, npf, gp, lds_p, sm);
-    }
-    t2.close();
-    if ((rc = check_launch("k_post"))) return fail(rc);
-#ifdef SNAKE_DIAG_ENC2
-    // Diagnostic timing build: k_post once more with idle workers (aux set), so
-    // the encodes alone are timed ("k_encode") with the same launch shape, LDS
-    // and registers; they rewrite the same observations.
-    if (!k.lean) {
-        const int epw2 = k.enc_per_wave, n16 = k.ring_bytes >> 4;
-        const int npw = (k.fs * k.HW / 4 + kWave - 1) / kWave;
-        const int npf = k.tbl ? (npw <= 2 ? -2 : -8)
-                              : (epw2 <= 1 ? 0 : (n16 <= kWave ? 1 : (n16 <= 2 * kWave ? 2 : 8)));
-        const int enc_blocks = npf == 0 ? k.N : (k.N + epw2 - 1) / epw2;
-        const dim3 gp(k.reset_slots + enc_blocks);
-        const int lds_p = std::max(k.lds_bytes, k.tbl ? k.lds_tbl_bytes : k.lds_obs_bytes);
-        const KArgs a2{k, st, o, (const void *)1};
-        TimedLaunch t5("k_encode", sm);
-        if (k.link32) launch_post_s<false, 2>(k, a2, npf, gp, lds_p, sm);
-        else launch_post_s<false, 1>(k, a2, npf, gp, lds_p, sm);
-        t5.close();
-    }
-#endif
-    return SNAKE_OK;
-}
-
 }  // namespace snake
 
-extern "C" int snake_timing_enable(int on)
-{
-    std::lock_guard<std::mutex> g(snake::g_tmu);
-    snake::g_timing = on != 0;
-    return SNAKE_OK;
-}
-
-#ifdef SNAKE_FUSE_DEBUG
-extern "C" int snake_debug_fdbg(unsigned long long *out)
-{
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(snake::g_fdbg), sizeof(unsigned long long) * 64) == hipSuccess ? 0 : -1;
-}
-#endif
-
-extern "C" int snake_debug_set(const char *name, long long value)
-{
-    if (name && value >= 0 && value <= INT_MAX) {
-        std::lock_guard<std::mutex> g(snake::g_tmu);
-        if (!strcmp(name, "draw_wait_ticks")) { snake::g_draw_wait_ticks = (int)value; return SNAKE_OK; }
-        if (!strcmp(name, "spawn_delay_ticks")) { snake::g_spawn_delay_ticks = (int)value; return SNAKE_OK; }
-        if (!strcmp(name, "fuse_roles")) { snake::g_fuse_roles = (int)value; return SNAKE_OK; }
-        if (!strcmp(name, "fused")) { snake::g_fused = value ? 1 : 0; return SNAKE_OK; }
-    }
-    snake::set_error("snake_debug_set: unknown knob or value out of range");
-    return SNAKE_E_ARG;
-}
-
-extern "C" int snake_timing_read(const char *kernel, double *total_ms, int64_t *count)
-{
-    if (!kernel || !total_ms || !count) {
-        snake::set_error("snake_timing_read: NULL argument");
-        return SNAKE_E_ARG;
-    }
-    const bool one = !strcmp(kernel, "resets") || !strcmp(kernel, "resets_timed");
-    const void *sym = !strcmp(kernel, "resets") ? (const void *)&snake::g_resets_run
-                    : !strcmp(kernel, "resets_timed") ? (const void *)&snake::g_resets_timed
-                    : !strcmp(kernel, "spawn_hits") ? (const void *)snake::g_spawn_hits
-                    : !strcmp(kernel, "spawn_jobs") ? (const void *)snake::g_spawn_jobs
-                    : !strcmp(kernel, "spawn_void") ? (const void *)snake::g_spawn_void
-                    : !strcmp(kernel, "reset_partial") ? (const void *)snake::g_reset_part
-                    : !strcmp(kernel, "respawn_slow") ? (const void *)snake::g_resp_slow
-                    : !strcmp(kernel, "respawn_slow2") ? (const void *)snake::g_resp_slow2
-                    : !strcmp(kernel, "gate_shut") ? (const void *)snake::g_gate_shut
-                    : !strcmp(kernel, "draw_wait") ? (const void *)snake::g_draw_wait
-                    : !strcmp(kernel, "draw_timeout") ? (const void *)snake::g_draw_timeout
-                    : !strcmp(kernel, "fused_timeout") ? (const void *)snake::g_fused_timeout : nullptr;
-    if (sym) {
-        const int n = one ? 1 : snake::kDiagSlots * snake::kDiagSpread;
-        std::vector<unsigned long long> v(n, 0ull), z(n, 0ull);
-        if (hipMemcpyFromSymbol(v.data(), sym, n * sizeof(unsigned long long)) != hipSuccess ||
-            hipMemcpyToSymbol(sym, z.data(), n * sizeof(unsigned long long)) != hipSuccess) {
-            snake::set_error("snake_timing_read: reading the reset counter failed");
-            return SNAKE_E_LAUNCH;
-        }
-        unsigned long long t = 0;
-        for (unsigned long long x : v) t += x;
-        *total_ms = 0.0;
-        *count = (int64_t)t;
-        return SNAKE_OK;
-    }
-    std::lock_guard<std::mutex> g(snake::g_tmu);
-    for (const auto &r : snake::g_pending) {
-        float ms = 0.f;
-        if (hipEventSynchronize(r.b) != hipSuccess || hipEventElapsedTime(&ms, r.a, r.b) != hipSuccess) {
-            snake::set_error("snake_timing_read: event query failed");
-            return SNAKE_E_LAUNCH;
-        }
-        auto &d = snake::g_done[r.name];
-        d.first += ms;
-        d.second += 1;
-        snake::g_pool.push_back(r.a);
-        snake::g_pool.push_back(r.b);
-    }
-    snake::g_pending.clear();
-    auto it = snake::g_done.find(kernel);
-    *total_ms = it == snake::g_done.end() ? 0.0 : it->second.first;
-    *count = it == snake::g_done.end() ? 0 : it->second.second;
-    if (it != snake::g_done.end()) snake::g_done.erase(it);
-    return SNAKE_OK;
-}
-
-#ifdef SNAKE_DRAWBENCH
-// (diagnostic build only: the isolated draw / attempt benchmarks and the
-// cooperative four-wave draws they compare against, scripts/microbench/)
+#include "snake_launch.inc"   // the host layer
+#ifdef SNAKE_DRAWBENCH   // (diagnostic build: the draw / attempt benchmarks, which use the device functions above)
 #include "../../scripts/microbench/drawbench.inc"
-#endif
-
-#ifdef SNAKE_STAMPS
-// out: 16 * 8192 per-wave phase realtimes of the last k_logic (g_wphase)
-extern "C" int snake_debug_wphase(unsigned long long *out)
-{
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(snake::g_wphase), sizeof(unsigned long long) * 16 * snake::kWaveTimes) ==
-                   hipSuccess ? 0 : -1;
-}
-
-// out: the reset workers' items of the launches since the last call (4 words
-// each, see g_items), at most cap; returns their number
-extern "C" int snake_debug_items(unsigned long long *out, int cap)
-{
-    unsigned n = 0, z = 0;
-    if (hipMemcpyFromSymbol(&n, HIP_SYMBOL(snake::g_nitems), sizeof n) != hipSuccess) return -1;
-    n = std::min<unsigned>(n, (unsigned)std::min(cap, snake::kItems));
-    if (n && hipMemcpyFromSymbol(out, HIP_SYMBOL(snake::g_items), sizeof(unsigned long long) * 4 * n) != hipSuccess)
-        return -1;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(snake::g_nitems), &z, sizeof z) != hipSuccess) return -1;
-    return (int)n;
-}
-
-// out: 64 phase stamps of block 0, 2 * 8192 k_logic wave start/end realtimes,
-// 2 * 40960 k_post block start/end realtimes
-extern "C" int snake_debug_stamps(unsigned long long *out)
-{
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(snake::g_stamps), sizeof(unsigned long long) * 64) != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out + 64, HIP_SYMBOL(snake::g_wavetime),
-                            sizeof(unsigned long long) * 2 * snake::kWaveTimes) != hipSuccess) return -1;
-    return hipMemcpyFromSymbol(out + 64 + 2 * snake::kWaveTimes, HIP_SYMBOL(snake::g_posttime),
-                               sizeof(unsigned long long) * 2 * snake::kPostTimes) == hipSuccess ? 0 : -1;
-}
 #endif

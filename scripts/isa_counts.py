@@ -2,10 +2,17 @@
 """Static instruction counts per kernel of snake_kernels.hip (gfx950 assembly):
 SGPR-spill lane moves (v_writelane / v_readlane: the compiler spills SGPRs into
 VGPR lanes), scratch accesses (VGPR spills), and the total, merged with the
-resource-usage remarks. One JSON object per kernel.
+resource-usage remarks. One JSON object per kernel, and one
+per device function that the compiler left out of line ("kind": "function").
 
-    python scripts/isa_counts.py [extra hipcc flags...] > profiles/r03_isa_counts.jsonl
+"body_sha" identifies the generated code: a hash of the function body with
+comment text dropped and the per-function number taken out of the .LBB<n>_<m>
+labels, so two builds whose records agree in name and body_sha run the same
+instructions.
+
+    python scripts/isa_counts.py [extra hipcc flags...] > profiles/isa_counts.jsonl
 """
+import hashlib
 import json
 import os
 import re
@@ -24,6 +31,11 @@ def demangle(name):
     return r.stdout.strip().replace('snake::', '') or name
 
 
+def body_sha(body):
+    lines = (re.sub(r'\.LBB\d+_', '.LBB_', ln.split(';')[0].rstrip()) for ln in body.splitlines())
+    return hashlib.sha256('\n'.join(ln for ln in lines if ln).encode()).hexdigest()[:16]
+
+
 def main():
     with tempfile.TemporaryDirectory() as d:
         asm = os.path.join(d, 'k.s')
@@ -40,16 +52,17 @@ def main():
             usage[cur] = {}
         elif m and cur:
             usage[cur][m.group(1).strip()] = m.group(2).strip()
-    # kernel bodies: from "<name>:" to its ".Lfunc_end"
+    kernels = set(re.findall(r'^\s*\.amdhsa_kernel\s+(\w+)', text, re.M))
+    # function bodies: from "<name>:" to its ".Lfunc_end"
     for m in re.finditer(r'^(_Z\w+):[^\n]*$(.*?)^\.Lfunc_end', text, re.S | re.M):
         name, body = m.group(1), m.group(2)
         ins = [ln.strip() for ln in body.splitlines()
                if ln.startswith('\t') and not ln.strip().startswith(('.', ';')) and ln.strip()]
         u = usage.get(name, {})
-        if not u:
-            continue
         print(json.dumps({
             'kernel': demangle(name),
+            'kind': 'kernel' if name in kernels else 'function',
+            'body_sha': body_sha(body),
             'instructions': len(ins),
             'v_writelane': sum(i.startswith('v_writelane') for i in ins),
             'v_readlane': sum(i.startswith('v_readlane') for i in ins),

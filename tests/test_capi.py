@@ -53,8 +53,8 @@ def test_plan_sizes(native):
     assert lay.grid_stride == 400 and lay.ring_cap == 512
     assert lay.spawn == 65536 * 672 * 4                        # spawn-ahead records
     assert lay.stats == 65536 * 4 * 16                         # snake_epi_stat: one 16-B record per snake
-    # two sets (step parity) of three queues + counters (one per 128-B line)
-    # two queue sets, then the fused step's counts, flags and hand-off records
+    # four queue sets (kQSets) of three queues + counters (one per 128-B line),
+    # then the fused step's counts, flags and hand-off records
     queues = 4 * (3 * 64 * (4096 // 64) * 16 + 227 * 32)   # (four queue sets)
     assert lay.resetq == (queues + 64 * 32 + 2 * 65536 // 4 + 4 * 65536) * 4
     c = cfg(native, height=40, width=40, num_snakes=8, vision_range=5, frame_stack=4)
@@ -158,3 +158,17 @@ def test_spawn_table_matches_reference(native):
     for H, W, L, C, dg in z['digest_meta']:
         t = table(native, int(H), int(W), int(L))
         assert t.shape[0] == int(C) and G.digest(t) == int(dg)
+
+
+def test_kernarg_pointer_only_at_kernel_entry():
+    """The kernarg-segment builtin means the running kernel's arguments only in
+    the kernel itself: it occurs once, in kernel_args(), and kernel_args() is
+    called only as the first statement of a __global__ function (device
+    functions take the pointer as an argument, inlined or not)."""
+    d = os.path.join(ROOT, 'marl-snake_amd', 'csrc')
+    src = '\n'.join(re.sub(r'//[^\n]*', '', open(os.path.join(d, f)).read()) for f in sorted(os.listdir(d)))
+    assert len(re.findall(r'KPtr kernel_args\(\)\s*\{[^}]*__builtin_amdgcn_kernarg_segment_ptr\(\)[^}]*\}', src)) == 1
+    assert src.count('__builtin_amdgcn_kernarg_segment_ptr') == 1
+    calls = len(re.findall(r'kernel_args\(\)', src)) - 1   # (less the definition)
+    entries = re.findall(r'__global__[^{;]*\{\s*const KPtr kp = kernel_args\(\);', src)
+    assert calls == len(entries) == 7

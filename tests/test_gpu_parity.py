@@ -147,6 +147,9 @@ BATCH_CASES = {
     'big_44_s4_global_links': (dict(height=44, width=44, snake_length=3, vision_range=4, spawn_ahead=4), 4, 16, 200),
     # 100x100: k_logic's eight frames per wave take 80 KB of LDS, one wave per workgroup
     'big_100_l2': (dict(height=100, width=100, snake_length=2, vision_range=3), 4, 16, 120),
+    # 40x40 x 4 frames with a 17x17 crop: the tables no longer fit beside the
+    # frames, k_post_lean with the lean (table-less) encode
+    'lean_40_s8_vr8_fs4': (dict(height=40, width=40, vision_range=8, frame_stack=4), 8, 16, 100),
     # the fused one-launch step (k_step: one frame, <= 4 snakes, table encode,
     # in-step spawn-ahead -- spawn_background=-1 keeps these small batches off
     # the background kernel): vision crop, full map, coop, human observer,
@@ -157,6 +160,8 @@ BATCH_CASES = {
     'fused_human_12_vr3': (dict(height=12, width=12, vision_range=3, observer='human', spawn_background=-1), 4, 64, 300),
     'fused_trunc_12_s2': (dict(height=12, width=12, max_episode_steps=7, spawn_background=-1), 2, 64, 100),
     'fused_s2_vr4': (dict(height=12, width=12, vision_range=4, num_fruits=6, spawn_background=-1), 2, 64, 300),
+    # 24x24: 144 frame dwords, three per lane (k_step / k_post with the 8-dword table encode)
+    'fused_24_vr3': (dict(height=24, width=24, vision_range=3, spawn_background=-1), 4, 64, 100),
 }
 
 
@@ -270,6 +275,11 @@ FULL_SIZE_CASES = {
     # the background spawn kernel (two library streams, 512 reset / spawn
     # workers, threshold 4): this is that default at its boundary
     'cfg3s8_8192': (8192, 4, 400, dict(height=20, width=20, snake_length=3, vision_range=5), 57344),
+    # widths that are no multiple of 4 (no table encode) at two envs per encode
+    # wave (16 384 envs and more): rings of at most 64 16-byte chunks (k_post's
+    # NPF = 1) and of 65 to 128 (NPF = 2)
+    'odd14_16384': (16384, 4, 100, dict(height=14, width=14, vision_range=3)),
+    'odd34_16384': (16384, 4, 120, dict(height=34, width=34, vision_range=3)),
 }
 
 
