@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SNAKE_ABI_VERSION 17
+#define SNAKE_ABI_VERSION 18
 
 #define SNAKE_OK           0
 #define SNAKE_E_CONFIG    -1   /* invalid snake_cfg (message says which field) */
@@ -320,6 +320,41 @@ int64_t snake_dqn32_scratch(const snake_dqn_cfg *cfg, int64_t batch);
 /* q_out: float [B][A]; feat_out (may be NULL): float [B][128]. Seven launches on `stream`. */
 int snake_dqn32_forward(const snake_dqn_cfg *cfg, const snake_dqn32_net *net, const uint8_t *obs,
                         int64_t batch, void *scratch, float *q_out, float *feat_out, void *stream);
+
+/* ---- Safe-action selection: the action rule of the reference's evaluator
+ * (train_dqn.py:433-580 DQN_Evaluator.get_action, driven by the loop at
+ * :625-646) for every env at once. Per env the snakes are taken in index order
+ * with an empty set of claimed cells. A snake whose skip byte is nonzero gets
+ * action 0 and keeps its direction. Otherwise its head is the first row-major
+ * cell with channel 5 == 1 (none: action 0, direction (0,0)); an unknown
+ * direction is read off the body cell behind the head (get_current_direction);
+ * the moves are {0: (dy,dx), 1: (-dx,dy), 2: (dx,-dy)}; a move's Q-value is
+ * masked to -inf when its target cell is outside the map, claimed by an earlier
+ * snake of the env, deadly (channel 0, 2, 3, 4, 6 or 7 == 1), beside a cell
+ * with channel 2 == 1, or opens into fewer reachable cells (flood fill, counted
+ * up to fill_limit) than the snake is long; the action is the first argmax of
+ * the masked values (all masked: 0), the direction becomes the chosen move and
+ * head + move is claimed. Cells are in each snake's own observation
+ * coordinates, as in the reference. NaN Q-values are outside the contract. */
+typedef struct {
+    int32_t obs_h, obs_w;   /* observation height and width, 1..64 */
+    int32_t obs_c;          /* observation channels: 8 (frame_stack 1) */
+    int32_t num_snakes;     /* S, 1..16 */
+    int32_t fill_limit;     /* flood-fill cap, 1..4096; the reference's is 60 */
+} snake_policy_cfg;
+
+#define SNAKE_DIR_UNKNOWN (-128)   /* both bytes of a direction not known yet */
+
+/* Validates cfg (host only, no device needed). */
+int snake_policy_plan(const snake_policy_cfg *cfg);
+
+/* obs: uint8 [N][S][h][w][8], 16-byte aligned; q: float [N][S][3]; skip: uint8
+ * [N][S] or NULL (no snake skipped); dirs: int8 [N][S][2] (dy,dx), read and
+ * updated in place; actions: int8 [N][S] out. One launch (k_safe_actions) on
+ * `stream`, on the stream's device. */
+int snake_safe_actions(const snake_policy_cfg *cfg, const uint8_t *obs, const float *q,
+                       const uint8_t *skip, int8_t *dirs, int8_t *actions, int64_t num_envs,
+                       void *stream);
 
 /* Last error message of this thread ("" if none). */
 const char *snake_last_error(void);

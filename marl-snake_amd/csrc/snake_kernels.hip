@@ -34,6 +34,7 @@
 #include <utility>
 
 #include "snake_internal.h"
+#include "snake_device.h"
 #include "snake_diag.h"
 
 constexpr int kResetWavesPerEU = 4;   // reset workers: 128 VGPRs (3 waves/SIMD measured slower)

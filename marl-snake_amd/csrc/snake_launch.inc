@@ -89,32 +89,8 @@ struct TimedLaunch {
     ~TimedLaunch() { close(); }
 };
 
-// Every launch runs with the caller stream's device current: the side stream and
-// events are created on it, and a SnakeVecEnv on cuda:1 works whatever device the
-// calling thread has current (restored on return).
-struct DeviceGuard {
-    int dev = -1, prev = -1;
-    explicit DeviceGuard(hipStream_t s)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) { set_error("hipGetDevice failed"); return; }
-        if (s == nullptr) { dev = prev; return; }
-        if (hipStreamGetDevice(s, &dev) != hipSuccess) {
-            set_error("hipStreamGetDevice failed");
-            dev = -1;
-            return;
-        }
-        if (dev != prev && hipSetDevice(dev) != hipSuccess) {
-            set_error("hipSetDevice(%d) failed", dev);
-            dev = -1;
-        }
-    }
-    ~DeviceGuard()
-    {
-        if (prev >= 0 && dev >= 0 && dev != prev) (void)hipSetDevice(prev);
-    }
-};
-
 // ---------------------------------------------------------------- launchers
+// (each under a DeviceGuard, snake_device.h)
 static int check_launch(const char *what)
 {
     const hipError_t err = hipGetLastError();

@@ -10,12 +10,13 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libsnake_amd.so')
 
-SNAKE_ABI_VERSION = 17
+SNAKE_ABI_VERSION = 18
 
 # Symbols include/snake_env.h declares (checked by tests/test_capi.py).
 EXPORTS = ('snake_plan', 'snake_build_candidates', 'snake_seed', 'snake_reset', 'snake_step',
            'snake_sync', 'snake_release', 'snake_render_rgb', 'snake_timing_enable', 'snake_timing_read', 'snake_debug_set', 'snake_last_error', 'snake_abi_version',
-           'snake_dqn_plan', 'snake_dqn_rows', 'snake_dqn_forward', 'snake_dqn32_scratch', 'snake_dqn32_forward')
+           'snake_dqn_plan', 'snake_dqn_rows', 'snake_dqn_forward', 'snake_dqn32_scratch', 'snake_dqn32_forward',
+           'snake_policy_plan', 'snake_safe_actions')
 
 
 class SnakeCfg(ctypes.Structure):
@@ -72,6 +73,10 @@ class Dqn32Net(ctypes.Structure):
         'fc2_b', 'fc3_b')]
 
 
+class PolicyCfg(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('obs_h', 'obs_w', 'obs_c', 'num_snakes', 'fill_limit')]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -116,6 +121,8 @@ def lib(path=None):
     L.snake_dqn32_scratch.argtypes = [ctypes.POINTER(DqnCfg), I64]
     L.snake_dqn32_scratch.restype = I64
     L.snake_dqn32_forward.argtypes = [ctypes.POINTER(DqnCfg), ctypes.POINTER(Dqn32Net), P, I64, P, P, P, P]
+    L.snake_policy_plan.argtypes = [ctypes.POINTER(PolicyCfg)]
+    L.snake_safe_actions.argtypes = [ctypes.POINTER(PolicyCfg), P, P, P, P, P, I64, P]
     L.snake_timing_enable.argtypes = [ctypes.c_int]
     L.snake_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_longlong]
     L.snake_timing_read.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_double),
