@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SNAKE_ABI_VERSION 18
+#define SNAKE_ABI_VERSION 19
 
 #define SNAKE_OK           0
 #define SNAKE_E_CONFIG    -1   /* invalid snake_cfg (message says which field) */
@@ -355,6 +355,85 @@ int snake_policy_plan(const snake_policy_cfg *cfg);
 int snake_safe_actions(const snake_policy_cfg *cfg, const uint8_t *obs, const float *q,
                        const uint8_t *skip, int8_t *dirs, int8_t *actions, int64_t num_envs,
                        void *stream);
+
+/* ---- Replay buffer: the reference trainer's deque of transitions
+ * (train_dqn.py:89-100 ReplayBuffer, filled at :290-298, sampled at :228-240)
+ * as rings in device memory, filled straight from one env step's tensors.
+ *
+ * Push. Snake (env, s) of the step is stored unless its skip byte is nonzero
+ * (`if not dones[i]`, :291); the stored snakes are appended in (env, snake)
+ * row-major order, which for one env is the reference's order. The stored
+ * reward is (float)(r + p) with the sum in double: p = early_death_penalty when
+ * the snake's done byte is nonzero, `step` is given and step[env] <
+ * early_death_steps, else 0 (:292-295; the rounding is torch.tensor(...,
+ * dtype=float32)'s at :238). done is stored as 0/1, the action as it is.
+ * The rings have deque(maxlen=capacity) semantics: `count`, a device int64, is
+ * the number of transitions ever stored and the only persistent counter; the
+ * transition with sequence number q lives in slot q % capacity, size =
+ * min(count, capacity), and logical index j in [0, size) -- the reference's
+ * buffer[j], 0 the oldest -- is sequence number count - size + j. A call that
+ * stores M > capacity transitions keeps the last `capacity` of them.
+ * Observations are 0/1 bytes (the env's; any nonzero byte packs as 1) and are
+ * stored bit-packed: the 8 channel bytes of one cell and frame, obs bytes
+ * [8g, 8g + 8) of a snake's row, are byte g of its packed row (bit k = channel
+ * k), h*w*obs_c/8 bytes per row at a 16-byte pitch.
+ *
+ * Gather. idx: int64 [B] logical indices, repeats allowed. An index is clamped
+ * into [0, max(size, 1)): a caller's mistake cannot read outside the rings,
+ * but an index outside [0, size) remains a contract violation. */
+typedef struct {
+    int32_t obs_h, obs_w;       /* observation height and width, 1..1024 */
+    int32_t obs_c;              /* observation channels: 8 * frame_stack, 8..512 */
+    int32_t num_snakes;         /* S, 1..16 */
+    int64_t capacity;           /* transitions the rings hold, 1..2^40 */
+    int32_t early_death_steps;  /* the reference's EARLY_DEATH_THRESHOLD (<= 0: never a penalty) */
+    double  early_death_penalty;/* the reference's EARLY_DEATH_PENALTY */
+} snake_replay_cfg;
+
+typedef struct {        /* byte sizes of the caller's device buffers */
+    int64_t state, next_state;  /* uint8 [capacity][pitch]: packed rows; zero them once */
+    int64_t action;             /* int8 [capacity] */
+    int64_t reward;             /* float [capacity] */
+    int64_t done;               /* uint8 [capacity] */
+    int64_t count;              /* one int64, zero = empty */
+    int64_t scratch;            /* snake_replay_push's scratch for num_envs envs (contents need not survive a call) */
+    int32_t packed_row, pitch;  /* h*w*obs_c/8, and that rounded up to 16 */
+} snake_replay_layout;
+
+typedef struct {        /* device buffers, sized by snake_replay_plan */
+    uint8_t *state, *next_state;
+    int8_t *action;
+    float *reward;
+    uint8_t *done;
+    int64_t *count;
+} snake_replay_rings;
+
+#define SNAKE_REPLAY_U8_NHWC  0   /* states as uint8 [B][h][w][C]: the bytes that were pushed */
+#define SNAKE_REPLAY_F32_NCHW 1   /* states as float [B][C][h][w], 0.0 / 1.0: x.permute(0,3,1,2).float() (:122) */
+
+/* Validates cfg (host only, no device needed; SNAKE_E_CONFIG names the field)
+ * and returns the buffer sizes for pushes of num_envs envs (0 .. 2^26). */
+int snake_replay_plan(const snake_replay_cfg *cfg, int64_t num_envs, snake_replay_layout *out);
+
+/* obs, next_obs: uint8 [N][S][h][w][C], 8-byte aligned; actions: int8 [N][S];
+ * rewards: double [N][S]; done: uint8 [N][S]; skip: uint8 [N][S] or NULL (every
+ * snake stored); step: int32 [N] or NULL (no penalty). Three launches on
+ * `stream` (k_replay_count, k_replay_scan, k_replay_store) whose grids depend
+ * on num_envs only; no host sync, the slots are assigned by a prefix count and
+ * do not vary from run to run. */
+int snake_replay_push(const snake_replay_cfg *cfg, const snake_replay_rings *rings, const uint8_t *obs,
+                      const uint8_t *next_obs, const int8_t *actions, const double *rewards,
+                      const uint8_t *done, const uint8_t *skip, const int32_t *step, int64_t num_envs,
+                      void *scratch, void *stream);
+
+/* idx: int64 [B]; state, next_state: 16-byte aligned, uint8 [B][h][w][C] or
+ * float [B][C][h][w] by `format`; action: int64 [B]; reward, done: float [B]
+ * (the dtypes of update_model's five tensors, :236-240). One launch
+ * (k_replay_gather_u8 / k_replay_gather_f32) on `stream`. B * h*w*obs_c/8 must
+ * be below 2^30. */
+int snake_replay_gather(const snake_replay_cfg *cfg, const snake_replay_rings *rings, const int64_t *idx,
+                        int64_t batch, int32_t format, void *state, void *next_state, int64_t *action,
+                        float *reward, float *done, void *stream);
 
 /* Last error message of this thread ("" if none). */
 const char *snake_last_error(void);

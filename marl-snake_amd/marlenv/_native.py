@@ -10,13 +10,14 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libsnake_amd.so')
 
-SNAKE_ABI_VERSION = 18
+SNAKE_ABI_VERSION = 19
 
 # Symbols include/snake_env.h declares (checked by tests/test_capi.py).
 EXPORTS = ('snake_plan', 'snake_build_candidates', 'snake_seed', 'snake_reset', 'snake_step',
            'snake_sync', 'snake_release', 'snake_render_rgb', 'snake_timing_enable', 'snake_timing_read', 'snake_debug_set', 'snake_last_error', 'snake_abi_version',
            'snake_dqn_plan', 'snake_dqn_rows', 'snake_dqn_forward', 'snake_dqn32_scratch', 'snake_dqn32_forward',
-           'snake_policy_plan', 'snake_safe_actions')
+           'snake_policy_plan', 'snake_safe_actions',
+           'snake_replay_plan', 'snake_replay_push', 'snake_replay_gather')
 
 
 class SnakeCfg(ctypes.Structure):
@@ -77,6 +78,22 @@ class PolicyCfg(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ('obs_h', 'obs_w', 'obs_c', 'num_snakes', 'fill_limit')]
 
 
+class ReplayCfg(ctypes.Structure):
+    _fields_ = [('obs_h', ctypes.c_int32), ('obs_w', ctypes.c_int32), ('obs_c', ctypes.c_int32),
+                ('num_snakes', ctypes.c_int32), ('capacity', ctypes.c_int64),
+                ('early_death_steps', ctypes.c_int32), ('early_death_penalty', ctypes.c_double)]
+
+
+class ReplayLayout(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in (
+        'state', 'next_state', 'action', 'reward', 'done', 'count', 'scratch')] + [
+        ('packed_row', ctypes.c_int32), ('pitch', ctypes.c_int32)]
+
+
+class ReplayRings(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ('state', 'next_state', 'action', 'reward', 'done', 'count')]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -123,6 +140,11 @@ def lib(path=None):
     L.snake_dqn32_forward.argtypes = [ctypes.POINTER(DqnCfg), ctypes.POINTER(Dqn32Net), P, I64, P, P, P, P]
     L.snake_policy_plan.argtypes = [ctypes.POINTER(PolicyCfg)]
     L.snake_safe_actions.argtypes = [ctypes.POINTER(PolicyCfg), P, P, P, P, P, I64, P]
+    L.snake_replay_plan.argtypes = [ctypes.POINTER(ReplayCfg), I64, ctypes.POINTER(ReplayLayout)]
+    L.snake_replay_push.argtypes = [ctypes.POINTER(ReplayCfg), ctypes.POINTER(ReplayRings), P, P, P, P, P, P, P,
+                                    I64, P, P]
+    L.snake_replay_gather.argtypes = [ctypes.POINTER(ReplayCfg), ctypes.POINTER(ReplayRings), P, I64,
+                                      ctypes.c_int32, P, P, P, P, P, P]
     L.snake_timing_enable.argtypes = [ctypes.c_int]
     L.snake_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_longlong]
     L.snake_timing_read.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_double),

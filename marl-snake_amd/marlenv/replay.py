@@ -1,0 +1,282 @@
+"""The reference trainer's replay buffer and rollout loop on the GPU.
+
+train_dqn.py's `--mode train` pushes one Transition(state, action, reward,
+next_state, done) per live snake and step into a deque(maxlen=BUFFER_SIZE)
+(train_dqn.py:89-100, :290-298) and update_model samples its batches from it
+(:228-240). ReplayBuffer is that deque in device memory, filled straight from a
+SnakeVecEnv's output tensors through snake_replay_push and read through
+snake_replay_gather (marl-snake_amd/csrc/replay_kernels.hip; the exact
+semantics are in include/snake_env.h); Collector is the vector form of the
+inner loop of Trainer.train (:277-308). Nothing on the way syncs with the host.
+
+Observations are 0/1 bytes in channel groups of 8, so the rings keep one byte
+per cell and frame: 1/8 of the memory of the tensors that were pushed. A byte
+that is neither 0 nor 1 comes back as 1.
+"""
+import ctypes
+
+from ._native import ReplayCfg, ReplayLayout, ReplayRings, check, lib
+
+FORMATS = {'uint8': 0, 'float32': 1}
+
+
+def _torch():
+    import torch
+    return torch
+
+
+class ReplayBuffer:
+    """deque(maxlen=capacity) of transitions, on the device.
+
+    obs_shape: (S, h, w, C), a SnakeVecEnv's obs_shape (C a multiple of 8, at
+    most 16 snakes; anything else raises ValueError). early_death: None or
+    (steps, penalty), the reference's EARLY_DEATH_THRESHOLD and
+    EARLY_DEATH_PENALTY: a snake that dies at an episode step below `steps` is
+    stored with reward + penalty. Logical index 0 is the oldest transition
+    held, len(buf) - 1 the newest, as in the reference's deque."""
+
+    def __init__(self, obs_shape, capacity, early_death=None, device=None, lib_path=None):
+        if len(obs_shape) != 4:
+            raise ValueError('obs_shape must be (S, h, w, C) (got %r)' % (tuple(obs_shape),))
+        S, h, w, c = (int(v) for v in obs_shape)
+        steps, penalty = (0, 0.0) if early_death is None else early_death
+        self._L = L = lib(lib_path)
+        self.cfg = ReplayCfg(h, w, c, S, int(capacity), int(steps), float(penalty))
+        self.layout = ReplayLayout()
+        check(L.snake_replay_plan(ctypes.byref(self.cfg), 0, ctypes.byref(self.layout)), L)   # ValueError before any device work
+        self.obs_shape = (S, h, w, c)
+        self.capacity = int(capacity)
+        self.device = _torch().device(device) if device is not None else None   # None: the first push's
+        self.count = None       # int64 (1,) on the device: transitions ever stored
+        self._rings = None
+        self._scratch = {}      # num_envs -> the push's scratch
+        self._keep = None
+
+    # ---------------------------------------------------------------- buffers
+    def _allocate(self, dev):
+        torch = _torch()
+        lay = self.layout
+
+        def zeros(nbytes):
+            return torch.zeros(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+
+        self.device = dev
+        self._state, self._next_state = zeros(lay.state), zeros(lay.next_state)
+        self._action, self._reward, self._done = zeros(lay.action), zeros(lay.reward), zeros(lay.done)
+        self.count = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._rings = ReplayRings(self._state.data_ptr(), self._next_state.data_ptr(), self._action.data_ptr(),
+                                  self._reward.data_ptr(), self._done.data_ptr(), self.count.data_ptr())
+
+    def _device_of(self, t, what):
+        dev = t.device
+        if dev.type != 'cuda':
+            raise ValueError('ReplayBuffer needs %s on the GPU (got %s); there is no CPU fallback' % (what, dev))
+        if self._rings is None and (self.device is None or (self.device.type == 'cuda' and self.device.index is None)):
+            self.device = dev
+        if dev != self.device:
+            raise ValueError('%s is on %s, this ReplayBuffer on %s' % (what, dev, self.device))
+        return dev
+
+    def _own_device(self):
+        torch = _torch()
+        if self._rings is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError('ReplayBuffer needs a HIP device (MI355X); there is no CPU fallback')
+            dev = self.device if self.device is not None else torch.device('cuda')
+            if dev.index is None:
+                dev = torch.device('cuda', torch.cuda.current_device())
+            self._allocate(dev)
+        return self.device
+
+    # -------------------------------------------------------------------- API
+    def push(self, obs, next_obs, actions, rewards, done, skip=None, step=None):
+        """One env step's transitions. obs, next_obs: contiguous uint8 (N, S, h,
+        w, C), the observations before and after the step; actions: int8 (N, S);
+        rewards: float64 (N, S); done: bool/uint8 (N, S), the dones after the
+        step; skip: bool/uint8 (N, S) or None -- snakes that were done before
+        the step and store nothing; step: int32 (N,) or None -- the index of
+        this step in each env's episode (0 for the first), for the early-death
+        penalty. Stored in (env, snake) order. Asynchronous on the current
+        stream; the inputs are kept alive until the next call."""
+        torch = _torch()
+        S = self.obs_shape[0]
+        for name, t in (('obs', obs), ('next_obs', next_obs)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_contiguous():
+                raise TypeError('ReplayBuffer.push takes %s as a contiguous uint8 tensor' % name)
+            if t.dim() != 5 or tuple(t.shape[1:]) != self.obs_shape:
+                raise ValueError('%s shape %s is not (N,) + %s' % (name, tuple(t.shape), self.obs_shape))
+        if next_obs.shape[0] != obs.shape[0]:
+            raise ValueError('obs holds %d envs, next_obs %d' % (obs.shape[0], next_obs.shape[0]))
+        N = obs.shape[0]
+        small = [('actions', actions, (torch.int8,), (N, S)), ('rewards', rewards, (torch.float64,), (N, S)),
+                 ('done', done, (torch.bool, torch.uint8), (N, S))]
+        if skip is not None:
+            small.append(('skip', skip, (torch.bool, torch.uint8), (N, S)))
+        if step is not None:
+            small.append(('step', step, (torch.int32,), (N,)))
+        for name, t, dtypes, shape in small:
+            if not isinstance(t, torch.Tensor) or t.dtype not in dtypes:
+                raise TypeError('ReplayBuffer.push takes %s as a %s tensor (got %s)' % (
+                    name, ' or '.join(str(d) for d in dtypes), getattr(t, 'dtype', type(t))))
+            if tuple(t.shape) != shape:
+                raise ValueError('%s shape %s is not %s' % (name, tuple(t.shape), shape))
+        dev = self._device_of(obs, 'obs')
+        for name, t in [('next_obs', next_obs)] + [(n, t) for n, t, _, _ in small]:
+            if t.device != dev:
+                raise ValueError('%s is on %s, obs on %s' % (name, t.device, dev))
+        if self._rings is None:
+            self._allocate(dev)
+        actions, rewards = actions.contiguous(), rewards.contiguous()
+        done = done.contiguous().view(torch.uint8)
+        if skip is not None:
+            skip = skip.contiguous().view(torch.uint8)
+        if step is not None:
+            step = step.contiguous()
+        scratch = self._scratch.get(N)
+        if scratch is None:
+            lay = ReplayLayout()
+            check(self._L.snake_replay_plan(ctypes.byref(self.cfg), N, ctypes.byref(lay)), self._L)
+            scratch = self._scratch[N] = torch.empty(int(lay.scratch), dtype=torch.uint8, device=dev)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        P = ctypes.c_void_p
+        with torch.cuda.device(dev):
+            check(self._L.snake_replay_push(
+                ctypes.byref(self.cfg), ctypes.byref(self._rings), P(obs.data_ptr()), P(next_obs.data_ptr()),
+                P(actions.data_ptr()), P(rewards.data_ptr()), P(done.data_ptr()),
+                P(skip.data_ptr()) if skip is not None else None,
+                P(step.data_ptr()) if step is not None else None, N, P(scratch.data_ptr()), stream), self._L)
+        self._keep = (obs, next_obs, actions, rewards, done, skip, step)
+
+    def size(self):
+        """min(count, capacity) as an int64 (1,) tensor on the device (no sync)."""
+        self._own_device()
+        return self.count.clamp(max=self.capacity)
+
+    def sample(self, batch_size=None, idx=None, format='uint8', replace=False, generator=None):
+        """(state, action, reward, next_state, done): update_model's five
+        tensors (train_dqn.py:236-240) -- action int64 (B,), reward and done
+        float32 (B,), and the states as
+          format='uint8':   uint8 (B, h, w, C), the bytes that were pushed (what
+                            DQNForward and the reference's DQN.forward take);
+          format='float32': float32 (B, C, h, w) of 0.0 / 1.0, what
+                            x.permute(0, 3, 1, 2).float() (:122) makes of them.
+        idx: int64 (B,) logical indices (0 the oldest; repeats allowed): a pure
+        gather. An index outside [0, len) is a contract violation (the kernel
+        clamps it so that it cannot read outside the rings). Without idx,
+        batch_size indices are drawn on the device from the device-side size,
+        without a host sync: replace=False (random.sample does not repeat) by
+        the top batch_size of random keys over the slots held, replace=True by
+        floor(u * size). The caller guarantees len(buf) >= batch_size (the
+        reference's MIN_BUFFER_SIZE guard). generator: a torch.Generator of the
+        buffer's device."""
+        torch = _torch()
+        if format not in FORMATS:
+            raise ValueError("format must be 'uint8' or 'float32' (got %r)" % (format,))
+        if idx is None:
+            if batch_size is None:
+                raise ValueError('sample needs batch_size or idx')
+            B = int(batch_size)
+            if B < 1 or (not replace and B > self.capacity):
+                raise ValueError('batch_size must be in [1, capacity] (got %d)' % B)
+            dev = self._own_device()
+            size = self.size()
+            if replace:
+                u = torch.rand(B, device=dev, generator=generator, dtype=torch.float64)
+                idx = torch.minimum((u * size).to(torch.int64), size - 1)
+            else:
+                keys = torch.rand(self.capacity, device=dev, generator=generator)
+                held = torch.arange(self.capacity, device=dev) < size
+                idx = torch.topk(keys.masked_fill_(~held, -1.0), B).indices
+        else:
+            if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64 or idx.dim() != 1:
+                raise TypeError('idx must be an int64 (B,) tensor')
+            dev = self._own_device()
+            if idx.device != dev:
+                raise ValueError('idx is on %s, this ReplayBuffer on %s' % (idx.device, dev))
+            idx = idx.contiguous()
+        B = idx.shape[0]
+        S, h, w, c = self.obs_shape
+        if format == 'uint8':
+            state = torch.empty((B, h, w, c), dtype=torch.uint8, device=dev)
+        else:
+            state = torch.empty((B, c, h, w), dtype=torch.float32, device=dev)
+        next_state = torch.empty_like(state)
+        action = torch.empty(B, dtype=torch.int64, device=dev)
+        reward = torch.empty(B, dtype=torch.float32, device=dev)
+        done = torch.empty(B, dtype=torch.float32, device=dev)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        P = ctypes.c_void_p
+        with torch.cuda.device(dev):
+            check(self._L.snake_replay_gather(
+                ctypes.byref(self.cfg), ctypes.byref(self._rings), P(idx.data_ptr()), B, FORMATS[format],
+                P(state.data_ptr()), P(next_state.data_ptr()), P(action.data_ptr()), P(reward.data_ptr()),
+                P(done.data_ptr()), stream), self._L)
+        self._keep_idx = idx
+        return state, action, reward, next_state, done
+
+    def __len__(self):
+        """Transitions held. Reads the device counter: this syncs with the host."""
+        if self.count is None:
+            return 0
+        return min(int(self.count.item()), self.capacity)
+
+    def clear(self):
+        """Forget every transition (the counter goes back to 0; no sync)."""
+        if self.count is not None:
+            self.count.zero_()
+
+
+class Collector:
+    """The vector form of the inner loop of Trainer.train (train_dqn.py:277-308):
+    epsilon-greedy actions from `qnet`, env.step, and one push per step into
+    `buffer`, all on the device.
+
+    env: a SnakeVecEnv with all-done auto-reset; buffer: a ReplayBuffer of
+    env.obs_shape. The collector resets the env and keeps the observations,
+    the per-snake "already done" mask (done & ~episode_done[:, None], the rule
+    of evaluate()) and a per-env int32 episode-step counter across run() calls.
+
+    Two deviations from the reference, both from the env's auto-reset:
+      - the next_state of an episode's last transitions is the next episode's
+        first observation; those transitions all have done = 1, so the TD
+        target (1 - done) * gamma * max Q(next_state) never reads it;
+      - an episode cut by the env's max_episode_steps is stored with done = 1,
+        where the reference's MAX_STEPS_PER_EPISODE cut stores done = 0."""
+
+    def __init__(self, env, buffer):
+        if tuple(buffer.obs_shape) != tuple(env.obs_shape):
+            raise ValueError('buffer obs_shape %s is not the env\'s %s' % (buffer.obs_shape, env.obs_shape))
+        torch = _torch()
+        self.env, self.buffer = env, buffer
+        N, S = env.num_envs, env.num_snakes
+        self.obs = env.reset()
+        self.mask = torch.zeros((N, S), dtype=torch.bool, device=env.device)
+        self.step_index = torch.zeros(N, dtype=torch.int32, device=env.device)
+
+    def run(self, qnet, steps, epsilon=0.0, generator=None):
+        """`steps` env steps. qnet: any callable from uint8 (N*S, h, w, C)
+        observations to float (N*S, 3) Q-values. Per snake u < epsilon gives a
+        uniform action in {0, 1, 2}, otherwise the argmax; a snake that is
+        already done gets action 0 (:281-285) and stores nothing. No host sync
+        inside the loop. generator: a torch.Generator of the env's device."""
+        torch = _torch()
+        env, buf = self.env, self.buffer
+        N, S = env.num_envs, env.num_snakes
+        _, h, w, c = env.obs_shape
+        dev = env.device
+        eps = float(epsilon)
+        for _ in range(int(steps)):
+            obs = self.obs
+            q = qnet(obs.view(N * S, h, w, c))
+            greedy = q.reshape(N, S, -1).argmax(dim=2)
+            if eps > 0.0:
+                u = torch.rand((N, S), device=dev, generator=generator)
+                rnd = torch.randint(0, 3, (N, S), device=dev, generator=generator)
+                greedy = torch.where(u < eps, rnd, greedy)
+            actions = greedy.masked_fill(self.mask, 0).to(torch.int8)
+            next_obs, rewards, done, info = env.step(actions)
+            ended = info['episode_done']
+            buf.push(obs, next_obs, actions, rewards, done, skip=self.mask, step=self.step_index)
+            self.obs = next_obs
+            self.mask = done & ~ended[:, None]
+            self.step_index = torch.where(ended, torch.zeros_like(self.step_index), self.step_index + 1)
