@@ -19,6 +19,12 @@
 #ifndef SNAKE_SPAWN_PRIO_SMALL   // (A/B builds: scripts/build_variants.sh)
 #define SNAKE_SPAWN_PRIO_SMALL 3
 #endif
+#ifndef SNAKE_LINK32_MAX_ENVS   // the u32 link table in LDS up to this many envs (table-encode boards; else 32 768)
+#define SNAKE_LINK32_MAX_ENVS 65536
+#endif
+#ifndef SNAKE_TBL_EPW           // envs per one-wave table-encode wave
+#define SNAKE_TBL_EPW 4
+#endif
 
 namespace snake {
 
@@ -477,16 +483,6 @@ int build_kcfg(const snake_cfg *c, int64_t N, int64_t n_cand, KCfg *k)
     // the LDS draw record: u16 per index < n_cand + one dummy slot per lane
     int jbytes = (int)round_up(2 * ((int64_t)k->n_cand + kWave), 16);
     k->link_in_lds = jbytes <= kJarrLdsMax;
-    // up to 32 768 envs the attempts' chain sets the shared phase: their link
-    // table as u32 in LDS (ds_min while drawing, then a pointer chase of ~ln n
-    // hops instead of scanning the u16 record: ~15 K of ~60 K cycles per
-    // attempt) -- cfg2 0.0451 -> 0.0430 ms, cfg4 0.0627 -> 0.0602; at 65 536
-    // envs the doubled LDS costs the encodes their occupancy (cfg3 0.0842 ->
-    // 0.0994), so there the u16 record stays
-    if (k->link_in_lds && N <= 32768 && !bg_of(c, n_cand, N) && 4 * (int64_t)k->link_stride <= kJarrLdsMax) {
-        k->link32 = 1;
-        jbytes = 4 * k->link_stride;
-    }
     // reset workers (<= kResetSlots, the global link tables are sized for that)
     k->reset_slots = (int)std::min<int64_t>(N, kResetSlots);
     const bool bg = bg_of(c, n_cand, N);
@@ -566,27 +562,67 @@ int build_kcfg(const snake_cfg *c, int64_t N, int64_t n_cand, KCfg *k)
         const int64_t fdw = (int64_t)k->fs * k->HW / 4;
         int t = 0;
         k->tbl_base = (int)round_up((int64_t)k->fs * k->pframe, 16); t = k->tbl_base + 8 * k->fs * kMaxSnakes;
-        k->tbl_pat = t; t += 8 * k->S * 160;   // (kPatV)
-        k->tbl_desc = t; t += (int)round_up(4 * (int64_t)k->units, 16);
-        k->lds_tbl_bytes = t;
-        k->tbl = g.exact && !g.lean && fdw <= 8 * kWave && t <= 40 * 1024 ? 1 : 0;
+        // patterns: the largest grid byte is 10 * (S - 1) + 5, so 10 * S entries per snake
+        k->tbl_patv = 10 * k->S;
+        k->tbl_pat = t; t += 8 * k->S * k->tbl_patv;
+        // descriptors: carved only where they are read from LDS -- the four-wave
+        // form, and one wave with more than four 16-byte chunks per lane (else
+        // each lane computes its four pairs into registers)
+        k->tbl_desc = t;
+        if (g.lean || k->units / 2 > 4 * kWave) t += (int)round_up(4 * (int64_t)k->units, 16);
+        k->lds_tbl_bytes = (int)round_up(t, 16);
+        auto mag = [](uint64_t d) { return (uint32_t)(((1ull << 32) + d - 1) / d); };
+        k->mag_nw = mag((uint64_t)std::max(1, k->HW / 4));
+        k->mag_npv = mag(3 + 3 * (uint64_t)k->S);
+        k->mag_S = mag((uint64_t)k->S);
+        // (which boards take the table encode is still decided on the size of
+        // the full carve -- 160 pattern entries per snake and the descriptors --
+        // that the measurements behind these limits had)
+        const int64_t t_full = k->tbl_pat + 8 * k->S * 160 + round_up(4 * (int64_t)k->units, 16);
+        k->tbl = g.exact && !g.lean && fdw <= 8 * kWave && t_full <= 40 * 1024 ? 1 : 0;
         // also in k_post_lean's four-wave workgroups (tables shared by the
         // workgroup, two envs each): cfg5 0.1023-0.1031 -> 0.1013-0.1015 ms; four
         // or eight envs per workgroup 0.107 / 0.111
-        if (g.lean && t <= 48 * 1024) k->tbl = 1;
+        if (g.lean && t_full <= 48 * 1024) k->tbl = 1;
     }
     // envs per encode wave (k_post's encodes: the next env's ring prefetched into
     // registers, at most 8 16-byte chunks per lane): two at 16 384 envs and more
     // (cfg3 0.1033 -> 0.0998 ms; 4, 8, 16, 32 measured 0.1016, 0.106, 0.114,
     // 0.135), one below (cfg2 0.0622 vs 0.0625); the lean encode two per workgroup
     k->enc_per_wave = k->lean ? 2 : (N >= 16384 && k->ring_bytes <= 8 * 1024 ? 2 : 1);
-    if (k->tbl) k->enc_per_wave = k->lean ? 2 : 4;   // (the tables are built once per wave; 8 measured slower at cfg3)
+    if (k->tbl) k->enc_per_wave = k->lean ? 2 : SNAKE_TBL_EPW;   // (the tables are built once per wave; 8 measured slower at cfg3)
     // (k_logic encoding the observations of its envs itself, from its LDS frames,
     // measured slower: cfg3 k_logic 24.8 -> 83.9 us against k_post 66.9 -> 57.6)
     // the reset workers never use the encode staging buffer: the draw record
     // overlays it (the workers' LDS is what k_encode's waves share the CUs with)
     k->lds_link = k->lds_stage;
+    // up to 32 768 envs the attempts' chain sets the shared phase: their link
+    // table as u32 in LDS (ds_min while drawing, then a pointer chase of ~ln n
+    // hops instead of scanning the u16 record: ~15 K of ~60 K cycles per
+    // attempt) -- cfg2 0.0451 -> 0.0430 ms, cfg4 0.0627 -> 0.0602. Above that the
+    // doubled LDS, charged to every one-wave encode workgroup, cost the encodes
+    // their occupancy (cfg3 0.0842 -> 0.0994). The table encode's workgroups of
+    // enc_wpb waves (below) share that charge, so with them the u32 table also
+    // wins at 65 536 envs (cfg3 0.0825 -> 0.0774 ms, profiles/r07_ab_encode_blocks.txt);
+    // larger batches are not measured and keep the u16 record
+    if (k->link_in_lds && !bg && 4 * (int64_t)k->link_stride <= kJarrLdsMax &&
+        (N <= 32768 || (N <= SNAKE_LINK32_MAX_ENVS && k->tbl && !k->lean))) {
+        k->link32 = 1;
+        jbytes = 4 * k->link_stride;
+    }
     k->lds_bytes = k->link_in_lds ? std::max(off, k->lds_stage + jbytes) : off;
+#ifndef SNAKE_ENC_WPB
+#define SNAKE_ENC_WPB kEncWpbMax
+#endif
+    // k_post's table-encode waves per workgroup: every workgroup of the launch,
+    // the workers' too, is charged the larger of the workers' LDS and enc_wpb
+    // table carves, so as many waves as keep that at the workers' own size or
+    // within 10 KB (16 workgroups per CU: the 8 workers and as many encode
+    // workgroups) -- the encodes' waves per CU are then set by their registers
+    k->enc_wpb = 1;
+    if (k->tbl && !k->lean)
+        for (int w = 2; w <= std::min((int)SNAKE_ENC_WPB, kEncWpbMax); w++)
+            if (w * k->lds_tbl_bytes <= std::max(k->lds_bytes, 10 * 1024)) k->enc_wpb = w;
     if (k->lds_bytes > 64 * 1024) {
         set_error("grid ring of %d bytes per env does not fit the LDS budget", k->ring_bytes);
         return SNAKE_E_CONFIG;

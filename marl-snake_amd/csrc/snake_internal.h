@@ -18,6 +18,7 @@ constexpr int kLdsLimit = 160 * 1024;   // LDS per workgroup (gfx950)
 // 2 560 (round 2: cfg3 0.0905 -> 0.0892 ms; 1 536 0.106); round 4: 2 560 and 3 072
 // equal (every spawn-ahead job a first job: cfg3 0.0838 / 0.0837), 1 792 0.1016
 constexpr int kResetSlots = 2048;
+constexpr int kEncWpbMax = 4;       // k_post: at most this many table-encode waves per workgroup (KCfg.enc_wpb)
 constexpr int kQShards = 64;        // auto-reset queue shards (k_logic block % 64)
 constexpr int kStageMax = 8192;     // bytes of staged observation per encode group
 constexpr int kSpawnStride = 672;   // u32 words per spawn-ahead record: key, pos, the poses' cells
@@ -115,10 +116,16 @@ struct KCfg {
     // multiply-high reciprocals of ups = oh*ow*fs, rowl = ow*fs, fs, and of W/4
     int lean, lp, pw, pframe, lds_lean_bytes, ups, rowl;
     // table encode in k_post (encode_tbl_block; the lean geometry above, one
-    // wave per env): its LDS carve -- the image at 0, window origins, patterns,
-    // unit descriptors
-    int tbl, tbl_base, tbl_pat, tbl_desc, lds_tbl_bytes;
+    // wave per env): its LDS carve -- the image at 0, window origins, patterns
+    // (tbl_patv = 10 * S entries per snake: the grid bytes that occur), and the
+    // unit descriptors where a lane's chunks take more than one pass (else the
+    // lanes keep them in registers and tbl_desc is not carved)
+    int tbl, tbl_base, tbl_pat, tbl_patv, tbl_desc, lds_tbl_bytes;
+    int enc_wpb;                // k_post: independent table-encode waves per workgroup (1 .. kEncWpbMax)
     uint32_t mag_ups, mag_rowl, mag_fs, mag_wpr;
+    // reciprocals of the table encode's setup: the frame's dwords H * W / 4, the
+    // occurring codes per snake 3 + 3 * S, and S
+    uint32_t mag_nw, mag_npv, mag_S;
     // fused step (k_step, snake_kernels.hip): on, the logic groups, the step's
     // epoch, and word offsets into resetq of the logic-done counts, the groups'
     // done and claim flags, and the encodes' hand-off records (uint4 per env)

@@ -2423,16 +2423,18 @@ __device__ __forceinline__ void encode_multi(const KCfg &c, const snake_state &s
 // unit (snake k, window row i, column j, frame f: obs (S, oh, ow, 8 fs)) the grid
 // byte v of frame f at that window cell comes from a zero-bordered LDS image of
 // the env's frames (no bounds test: cells outside the grid read 0), and the
-// unit's 8 one-hot channels are the table entry pat[k][v] (onehot()). A lane's
-// units are the same for every env: their descriptors desc[u] = (i * pw + j) |
-// (f * 16 + k) << 16 are built once per wave, and per env only the window
-// origins base[f * 16 + k] = (LDS byte of the window origin in frame f, byte
-// offset of pat[k]) change. Per 16-byte store: one descriptor pair, two window
-// origins, two grid bytes and two patterns from LDS, four address adds. The
-// next env's frames (NPW dwords per lane), slot, crop centres and reset flag
-// are loaded into registers during this env's encode (as encode_lean_block).
-constexpr int kPatV = 160;   // grid byte values 10 * id + code (id < 16, code <= 5)
-
+// unit's 8 one-hot channels are the table entry pat[k][v] (onehot(); v < 10 * S,
+// so c.tbl_patv = 10 * S entries per snake). A lane's units are the same for
+// every env: their descriptors desc[u] = (i * pw + j) | (f * 16 + k) << 16 are
+// built once per wave -- straight into registers where a lane's chunks take
+// one pass, else into an LDS table -- and per env only the window origins
+// base[f * 16 + k] = (LDS byte of the window origin in frame f, byte offset of
+// pat[k]) change. Per 16-byte store: one descriptor pair, two window origins,
+// two grid bytes and two patterns from LDS, four address adds. The next env's
+// frames (NPW dwords per lane), slot, crop centres and reset flag are loaded
+// into registers during this env's encode (as encode_lean_block); the first
+// env's before the wave's setup, so that round trip runs beside it. The
+// setup's divisions are multiply-highs by plan-time reciprocals (mag_*).
 template <int T>
 __device__ __forceinline__ void tsync()
 {
@@ -2442,19 +2444,24 @@ __device__ __forceinline__ void tsync()
 
 // FU (k_step): the frames and the hand-off record (slot, reset flag, crop
 // centres) of the logic wave that finished these envs in this launch, all read
-// with write-through-coherent (sc1) loads after its done flag
-template <int NPW, int T = kWave, bool FU = false>
-__device__ void encode_tbl_block(const KCfg &c, const snake_state &st, const snake_out &o, const int blk)
+// with write-through-coherent (sc1) loads after its done flag.
+// One-wave form (T = kWave): `wave` = this wave's index in its workgroup
+// (k_post runs c.enc_wpb independent encode waves per workgroup, each on its
+// own c.lds_tbl_bytes of LDS and synchronising at wave level only).
+template <int NPW, int T, bool FU>
+__device__ __forceinline__ void encode_tbl_body(const KCfg &c, const snake_state &st, const snake_out &o, const int blk,
+                                                const int wave)
 {
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const int lane = threadIdx.x;
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds0[];
+    uint8_t *lds = lds0 + wave * c.lds_tbl_bytes;
+    const int lane = threadIdx.x & (T - 1);
     if (c.encode_prio == 1) __builtin_amdgcn_s_setprio(1);
     else if (c.encode_prio == 2) __builtin_amdgcn_s_setprio(2);
     else if (c.encode_prio == 3) __builtin_amdgcn_s_setprio(3);
     uint8_t *pf = lds;                                                   // fs * pframe bytes
     uint2 *base = reinterpret_cast<uint2 *>(lds + c.tbl_base);           // [fs][16]
-    uint8_t *pat = lds + c.tbl_pat;                                      // uint2 [S][kPatV]
-    uint32_t *desc = reinterpret_cast<uint32_t *>(lds + c.tbl_desc);     // [units]
+    uint8_t *pat = lds + c.tbl_pat;                                      // uint2 [S][c.tbl_patv]
+    uint32_t *desc = reinterpret_cast<uint32_t *>(lds + c.tbl_desc);     // [units] (carved for the multi-pass forms only)
     const int S = c.S, fs = c.fs, fsS = fs * S;
     const int wpr = c.W >> 2, nw = c.H * wpr, nwt = fs * nw, gsw = c.grid_stride >> 2;
     // per prefetched dword: ring word index and LDS dword index (clamped: the
@@ -2463,31 +2470,15 @@ __device__ void encode_tbl_block(const KCfg &c, const snake_state &st, const sna
 #pragma unroll
     for (int u = 0; u < NPW; u++) {
         const int x = min(lane + u * T, nwt - 1);
-        const int s = x / nw, xx = x - s * nw;
+        const int s = fdiv((uint32_t)x, c.mag_nw, nw), xx = x - s * nw;
         const int r = fdiv((uint32_t)xx, c.mag_wpr, wpr), c4 = xx - r * wpr;
         src[u] = s * gsw + xx;
         dst[u] = (s * c.pframe + (r + c.vr) * c.pw + c.lp) / 4 + c4;
     }
-    // once per wave: the zero image, the patterns of the codes that occur (0, 1,
-    // 2 and 10 * id + 3..5 for id < S), the unit descriptors
-    zero_lean<T>(c, pf, lane);
-    const int npv = 3 + 3 * S;   // occurring codes per snake
-    for (int x = lane; x < S * npv; x += T) {
-        const int k = x / npv, r = x - k * npv;
-        const int v = r < 3 ? r : 10 * ((r - 3) / 3) + 3 + (r - 3) % 3;
-        const unsigned long long b = onehot(v, k);
-        reinterpret_cast<uint2 *>(pat)[k * kPatV + v] = make_uint2((uint32_t)b, (uint32_t)(b >> 32));
-    }
-    for (int u = lane; u < c.units; u += T) {
-        const int kk = (int)__umulhi((uint32_t)u, c.mag_ups), r0 = u - kk * c.ups;
-        const int ii = (int)__umulhi((uint32_t)r0, c.mag_rowl), r1 = r0 - ii * c.rowl;
-        const int jj = fdiv((uint32_t)r1, c.mag_fs, fs), ff = r1 - jj * fs;
-        desc[u] = (uint32_t)(ii * c.pw + jj) | ((uint32_t)(ff * kMaxSnakes + kk) << 16);
-    }
     const int e_begin = blk * c.enc_per_wave, e_end = min(c.N, e_begin + c.enc_per_wave);
     uint32_t w[NPW];
     int pcur = 0, pctr = 0, pskip = 0;
-#define SNAKE_TBL_FETCH(EE)                                                                        \
+#define SNAKE_TBL_FETCH(EE)                                                                  \
     do {                                                                                           \
         const int64_t e_ = (EE);                                                                   \
         const uint32_t *r32_ = reinterpret_cast<const uint32_t *>(st.grid + e_ * c.ring_bytes);    \
@@ -2504,17 +2495,41 @@ __device__ void encode_tbl_block(const KCfg &c, const snake_state &st, const sna
             pskip = c.autoreset ? o.ep_done[e_] : 0;                                               \
         }                                                                                          \
     } while (0)
+    // the first env's frames, slot, centres and reset flag: issued before the
+    // setup below, so their memory round trip runs beside it
     if (e_begin < e_end) SNAKE_TBL_FETCH(e_begin);
+    // once per wave: the zero image, the patterns of the codes that occur (0, 1,
+    // 2 and 10 * id + 3..5 for id < S; c.tbl_patv entries per snake), the unit
+    // descriptors
+    zero_lean<T>(c, pf, lane);
+    const int npv = 3 + 3 * S, patv = c.tbl_patv;   // occurring codes per snake, table entries per snake
+    for (int x = lane; x < S * npv; x += T) {
+        const int k = (int)__umulhi((uint32_t)x, c.mag_npv), r = x - k * npv;
+        const int v = r < 3 ? r : 10 * ((r - 3) / 3) + 3 + (r - 3) % 3;
+        const unsigned long long b = onehot(v, k);
+        reinterpret_cast<uint2 *>(pat)[k * patv + v] = make_uint2((uint32_t)b, (uint32_t)(b >> 32));
+    }
+    auto desc_of = [&](const int u) {
+        const int kk = (int)__umulhi((uint32_t)u, c.mag_ups), r0 = u - kk * c.ups;
+        const int ii = (int)__umulhi((uint32_t)r0, c.mag_rowl), r1 = r0 - ii * c.rowl;
+        const int jj = fdiv((uint32_t)r1, c.mag_fs, fs), ff = r1 - jj * fs;
+        return (uint32_t)(ii * c.pw + jj) | ((uint32_t)(ff * kMaxSnakes + kk) << 16);
+    };
     const int chunks = c.units >> 1;
-    // a lane's chunks all in one pass (cfg3: 242 chunks): their descriptors in
-    // registers for every env of the wave, one LDS level less per lookup chain
+    // a lane's chunks all in one pass (cfg3: 242 chunks): their descriptors
+    // computed straight into registers for every env of the wave -- no LDS
+    // table (build_kcfg does not carve it), one LDS level less per lookup chain
     const bool one = T == kWave && chunks <= 4 * T;
     uint2 dr[4];
     if constexpr (T == kWave) if (one) {
-        tsync<T>();
 #pragma unroll
-        for (int t = 0; t < 4; t++) dr[t] = reinterpret_cast<const uint2 *>(desc)[min(t * T + lane, chunks - 1)];
+        for (int t = 0; t < 4; t++) {
+            const int q = min(t * T + lane, chunks - 1);
+            dr[t] = make_uint2(desc_of(2 * q), desc_of(2 * q + 1));
+        }
     }
+    if (!one)
+        for (int u = lane; u < c.units; u += T) desc[u] = desc_of(u);
     for (int e = e_begin; e < e_end; e++) {
         const int cur = pcur, skip = pskip;   // (a reset env's obs is written by its reset)
         tsync<T>();                          // (the previous encode has read the LDS image)
@@ -2523,11 +2538,11 @@ __device__ void encode_tbl_block(const KCfg &c, const snake_state &st, const sna
             for (int u = 0; u < NPW; u++) reinterpret_cast<uint32_t *>(pf)[dst[u]] = w[u];
             if (lane < fsS) {
                 // ring slot s = lane / S holds frame f = s - (the oldest slot), mod fs
-                const int s = lane / S, k = lane - s * S, slot0 = cur + 1 == fs ? 0 : cur + 1;
+                const int s = fdiv((uint32_t)lane, c.mag_S, S), k = lane - s * S, slot0 = cur + 1 == fs ? 0 : cur + 1;
                 const int f = s >= slot0 ? s - slot0 : s - slot0 + fs;
                 const uint32_t gb = (uint32_t)(s * c.pframe) +
                                     (c.vr ? (uint32_t)((pctr >> 8) * c.pw + (pctr & 255) + c.lp - c.vr) : 0u);
-                base[f * kMaxSnakes + k] = make_uint2(gb, (uint32_t)(k * kPatV * 8));
+                base[f * kMaxSnakes + k] = make_uint2(gb, (uint32_t)(k * patv * 8));
             }
         }
         if (e + 1 < e_end) SNAKE_TBL_FETCH(e + 1);   // in flight during this env's encode
@@ -2566,6 +2581,26 @@ __device__ void encode_tbl_block(const KCfg &c, const snake_state &st, const sna
         }
     }
 #undef SNAKE_TBL_FETCH
+}
+
+// Inlined into its kernels, except the one-wave form with eight frame dwords
+// per lane (larger boards, 16 kernels): that one stays a function, as the
+// inliner had left it. Pinned here because the setup's size decides the
+// inliner's choice otherwise, and an out-of-line two-dword form costs k_post
+// 118 VGPRs instead of 71.
+template <bool FU>
+__device__ __noinline__ void encode_tbl_block8(const KCfg &c, const snake_state &st, const snake_out &o, const int blk,
+                                               const int wave)
+{
+    encode_tbl_body<8, kWave, FU>(c, st, o, blk, wave);
+}
+
+template <int NPW, int T = kWave, bool FU = false>
+__device__ __forceinline__ void encode_tbl_block(const KCfg &c, const snake_state &st, const snake_out &o, const int blk,
+                                                 const int wave = 0)
+{
+    if constexpr (NPW == 8 && T == kWave) encode_tbl_block8<FU>(c, st, o, blk, wave);
+    else encode_tbl_body<NPW, T, FU>(c, st, o, blk, wave);
 }
 
 // ------------------------------------------------------------ fused step
@@ -2723,13 +2758,22 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) k_
 }
 
 // NPF > 0: encode_multi<NPF>; 0: encode_one; -NPW: encode_tbl_block<NPW>
+// Table encode (NPF < 0): workgroups of c.enc_wpb waves. In a worker workgroup
+// only wave 0 works, the others return at once; wave w of encode workgroup b
+// encodes env group (b - G) * enc_wpb + w on its own LDS slice, no workgroup
+// barrier anywhere (as k_logic's four waves) -- the launch's LDS, the larger
+// of the workers' record and enc_wpb table carves, is then charged once per
+// enc_wpb encode waves instead of once per wave.
 template <int MS, int NPF, bool RO, int JL>
-__global__ void __launch_bounds__(64) k_post(const KArgs)
+__global__ void __launch_bounds__(NPF < 0 ? kWave * kEncWpbMax : kWave) k_post(const KArgs)
 {
     const KPtr kp = kernel_args();
     PTIME(0);
     const int G = kargs(kp).c.reset_slots, b = (int)blockIdx.x;
+    int wave = 0;
+    if constexpr (NPF < 0) wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (b < G) {
+        if (wave) return;
         extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
 #ifdef SNAKE_DIAG_ENC2   // (diagnostic: the second, encode-only launch, see launch_step)
         if (kargs(kp).aux) return;
@@ -2741,7 +2785,11 @@ __global__ void __launch_bounds__(64) k_post(const KArgs)
 #endif
         const KArgs &A = kargs(kp);
         if constexpr (NPF == 0) encode_one(A.c, A.st, A.o, b - G);
-        else if constexpr (NPF < 0) encode_tbl_block<-NPF>(A.c, A.st, A.o, b - G);
+        else if constexpr (NPF < 0) {
+            const int grp = (b - G) * A.c.enc_wpb + wave;
+            if (grp * A.c.enc_per_wave >= A.c.N) return;   // (the last workgroup's spare waves)
+            encode_tbl_block<-NPF>(A.c, A.st, A.o, grp, wave);
+        }
         else encode_multi<NPF>(A.c, A.st, A.o, b - G);
     }
     PTIME(1);

@@ -274,9 +274,11 @@ static PostShape post_shape(const KCfg &k)
     const int n16 = k.ring_bytes >> 4;
     const int npw = (k.fs * k.HW / 4 + kWave - 1) / kWave;   // frame dwords per lane (table encode)
     const int npf = k.tbl ? (npw <= 2 ? -2 : -8) : (epw <= 1 ? 0 : (n16 <= kWave ? 1 : (n16 <= 2 * kWave ? 2 : 8)));
-    const int enc_blocks = npf == 0 ? k.N : (k.N + epw - 1) / epw;
-    return {npf, dim3(k.reset_slots + enc_blocks), dim3(kWave),
-            std::max(k.lds_bytes, k.tbl ? k.lds_tbl_bytes : k.lds_obs_bytes)};
+    const int enc_waves = npf == 0 ? k.N : (k.N + epw - 1) / epw;
+    // the table encode: enc_wpb independent waves per workgroup, each with its own carve
+    const int wpb = k.tbl ? k.enc_wpb : 1;
+    return {npf, dim3(k.reset_slots + (enc_waves + wpb - 1) / wpb), dim3(kWave * wpb),
+            std::max(k.lds_bytes, k.tbl ? wpb * k.lds_tbl_bytes : k.lds_obs_bytes)};
 }
 
 // k_post_lean<MS(S), RO(bg), TBL> or k_post<MS(S), NPF, RO, JL>: resets only (ro: background
