@@ -435,6 +435,104 @@ int snake_replay_gather(const snake_replay_cfg *cfg, const snake_replay_rings *r
                         int64_t batch, int32_t format, void *state, void *next_state, int64_t *action,
                         float *reward, float *done, void *stream);
 
+/* ---- Genome heads: a population of NEAT feed-forward networks, one genome
+ * per env (train_ga.py:224-257 eval_genomes: every live snake's 128 features of
+ * the frozen DQN go through the genome's neat.nn.FeedForwardNetwork, the action
+ * is np.argmax of its outputs; train_dqn.py:725-772 HybridNEATEnemy is the same
+ * head).
+ *
+ * A population is packed once into one flat program. Genome g owns the nodes
+ * [node_off[g], node_off[g + 1]) in evaluation order (FeedForwardNetwork's
+ * node_evals); node n owns the links [link_off[n], link_off[n + 1]) in order.
+ * Values live in slots: slots 0 .. I-1 are the inputs, slot I + k is the
+ * genome's k-th node, so a link's source slot is below its node's slot. Per
+ * feature row the result is, in IEEE double with no fused multiply-add,
+ *     s = +0.0;  for each link in order: s = s + value[src] * weight
+ *     value[I + k] = act(bias + response * s)
+ * with the inputs the float features widened to double (numpy 1.21, which the
+ * reference pins: float32 scalar * Python float is float64), and act one of
+ *     relu     z > 0.0 ? z : 0.0
+ *     sigmoid  z = max(-60, min(60, 5 z));   1 / (1 + exp(-z))
+ *     tanh     z = max(-60, min(60, 2.5 z)); tanh(z)
+ * (neat-python's relu_, sigmoid_ and tanh_activation; the aggregation is sum).
+ * Output a is the value of slot out_slot[g][a], or 0.0 where that is -1 (an
+ * output key no node evaluates keeps activate()'s initial 0.0). The action is
+ * the first maximum of the outputs; a row whose skip byte is nonzero gets
+ * action 0 (train_ga.py:236; its outputs are still computed). relu-only
+ * programs are exact; exp and tanh are the device library's. NaN or infinite
+ * weights and features are outside the contract. */
+#define SNAKE_GENOME_RELU    0
+#define SNAKE_GENOME_SIGMOID 1
+#define SNAKE_GENOME_TANH    2
+
+typedef struct {
+    int32_t num_inputs;     /* I, 1..1024 */
+    int32_t num_outputs;    /* A, 1..16 */
+    int32_t num_genomes;    /* G, 1..2^20 */
+    int32_t max_nodes;      /* nodes of the largest genome */
+    int64_t num_nodes;      /* nodes of all genomes, 0..2^30 */
+    int64_t num_links;      /* links of all nodes, 0..2^30 */
+} snake_genome_cfg;
+
+typedef struct {        /* the packed program: host arrays for snake_genome_check, device arrays for the launch */
+    const int32_t *node_off;    /* [G + 1], from 0 to num_nodes */
+    const int32_t *node_act;    /* [num_nodes] SNAKE_GENOME_RELU / _SIGMOID / _TANH */
+    const double *node_bias;    /* [num_nodes] */
+    const double *node_resp;    /* [num_nodes] response */
+    const int32_t *link_off;    /* [num_nodes + 1], from 0 to num_links */
+    const int32_t *link_src;    /* [num_links] source slot */
+    const double *link_w;       /* [num_links] */
+    const int32_t *out_slot;    /* [G][A] slot of output a, -1: never evaluated */
+} snake_genome_prog;
+
+typedef struct {        /* up to tile_rows feature rows of one genome: the work of one wave */
+    int32_t genome;
+    int32_t count;          /* rows, 1..tile_rows */
+    int32_t row_start;      /* the rows are rows[row_start .. row_start + count) */
+    int32_t scratch;        /* index of the tile's slice of the scratch buffer, -1: node values in LDS */
+} snake_genome_tile;
+
+typedef struct {
+    int64_t scratch;        /* bytes of snake_genome_actions' scratch (0: every genome's node values fit LDS) */
+    int64_t max_tiles;      /* the most tiles snake_genome_tiles makes of that many rows */
+    int32_t tile_rows;      /* rows per tile: 64, fewer where 64 rows of I features do not fit LDS */
+    int32_t lds_nodes;      /* genomes of more nodes keep their node values in the scratch buffer */
+    int32_t lds_bytes;      /* dynamic LDS of the launch */
+} snake_genome_layout;
+
+/* Validates cfg (host only, no device needed; SNAKE_E_CONFIG names the field)
+ * and returns the sizes for launches over `rows` feature rows (0 .. 2^30). */
+int snake_genome_plan(const snake_genome_cfg *cfg, int64_t rows, snake_genome_layout *out);
+
+/* Checks a packed program in HOST memory against cfg (host only): SNAKE_E_CONFIG
+ * names the field when node_off or link_off is not monotone from 0 to its total,
+ * a node_act is not an activation id, a link_src is not below its node's slot,
+ * an out_slot is outside [-1, I + the genome's nodes), or max_nodes is not the
+ * largest genome's node count. The kernel trusts these indices: upload a
+ * program only after this call has returned SNAKE_OK. */
+int snake_genome_check(const snake_genome_cfg *cfg, const snake_genome_prog *host_prog);
+
+/* Groups the N * S feature rows (row = env * S + snake) by genome (host only).
+ * node_off: the program's, host; genome_of_env: int32 [N], any order, repeats
+ * allowed; rows: int32 [N * S] out, the rows ordered by genome (envs of one
+ * genome in index order); tiles: out, at most tile_cap of them, or NULL to count.
+ * Returns the number of tiles (at most snake_genome_layout.max_tiles) or a
+ * negative error. Upload both arrays as they are for snake_genome_actions. */
+int64_t snake_genome_tiles(const snake_genome_cfg *cfg, const int32_t *node_off,
+                           const int32_t *genome_of_env, int64_t num_envs, int32_t num_snakes,
+                           int32_t *rows, snake_genome_tile *tiles, int64_t tile_cap);
+
+/* prog: device arrays that passed snake_genome_check; tiles, rows: device copies
+ * of snake_genome_tiles' output for the same cfg; features: float [num_rows][I];
+ * skip: uint8 [num_rows] or NULL; actions: int8 [num_rows] out; outputs: double
+ * [num_rows][A] out or NULL; scratch: snake_genome_layout.scratch bytes for
+ * num_rows rows (may be NULL when that is 0; contents need not survive a call).
+ * One launch (k_genome_actions) on `stream`, on the stream's device. */
+int snake_genome_actions(const snake_genome_cfg *cfg, const snake_genome_prog *prog,
+                         const snake_genome_tile *tiles, const int32_t *rows, int64_t num_tiles,
+                         const float *features, const uint8_t *skip, int8_t *actions, double *outputs,
+                         void *scratch, int64_t num_rows, void *stream);
+
 /* Last error message of this thread ("" if none). */
 const char *snake_last_error(void);
 

@@ -17,7 +17,8 @@ EXPORTS = ('snake_plan', 'snake_build_candidates', 'snake_seed', 'snake_reset', 
            'snake_sync', 'snake_release', 'snake_render_rgb', 'snake_timing_enable', 'snake_timing_read', 'snake_debug_set', 'snake_last_error', 'snake_abi_version',
            'snake_dqn_plan', 'snake_dqn_rows', 'snake_dqn_forward', 'snake_dqn32_scratch', 'snake_dqn32_forward',
            'snake_policy_plan', 'snake_safe_actions',
-           'snake_replay_plan', 'snake_replay_push', 'snake_replay_gather')
+           'snake_replay_plan', 'snake_replay_push', 'snake_replay_gather',
+           'snake_genome_plan', 'snake_genome_check', 'snake_genome_tiles', 'snake_genome_actions')
 
 
 class SnakeCfg(ctypes.Structure):
@@ -94,6 +95,25 @@ class ReplayRings(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ('state', 'next_state', 'action', 'reward', 'done', 'count')]
 
 
+class GenomeCfg(ctypes.Structure):
+    _fields_ = [('num_inputs', ctypes.c_int32), ('num_outputs', ctypes.c_int32), ('num_genomes', ctypes.c_int32),
+                ('max_nodes', ctypes.c_int32), ('num_nodes', ctypes.c_int64), ('num_links', ctypes.c_int64)]
+
+
+class GenomeProg(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in (
+        'node_off', 'node_act', 'node_bias', 'node_resp', 'link_off', 'link_src', 'link_w', 'out_slot')]
+
+
+class GenomeTile(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('genome', 'count', 'row_start', 'scratch')]
+
+
+class GenomeLayout(ctypes.Structure):
+    _fields_ = [('scratch', ctypes.c_int64), ('max_tiles', ctypes.c_int64), ('tile_rows', ctypes.c_int32),
+                ('lds_nodes', ctypes.c_int32), ('lds_bytes', ctypes.c_int32)]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -145,6 +165,12 @@ def lib(path=None):
                                     I64, P, P]
     L.snake_replay_gather.argtypes = [ctypes.POINTER(ReplayCfg), ctypes.POINTER(ReplayRings), P, I64,
                                       ctypes.c_int32, P, P, P, P, P, P]
+    L.snake_genome_plan.argtypes = [ctypes.POINTER(GenomeCfg), I64, ctypes.POINTER(GenomeLayout)]
+    L.snake_genome_check.argtypes = [ctypes.POINTER(GenomeCfg), ctypes.POINTER(GenomeProg)]
+    L.snake_genome_tiles.argtypes = [ctypes.POINTER(GenomeCfg), P, P, I64, ctypes.c_int32, P, P, I64]
+    L.snake_genome_tiles.restype = I64
+    L.snake_genome_actions.argtypes = [ctypes.POINTER(GenomeCfg), ctypes.POINTER(GenomeProg), P, P, I64, P, P, P, P,
+                                       P, I64, P]
     L.snake_timing_enable.argtypes = [ctypes.c_int]
     L.snake_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_longlong]
     L.snake_timing_read.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_double),

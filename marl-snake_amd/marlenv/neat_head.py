@@ -1,0 +1,297 @@
+"""A population of NEAT decision heads on the GPU, one genome per env.
+
+train_ga.py's eval_genomes (:224-257) gives each genome of a generation one env:
+at every step the 128 features of the frozen DQN of each live snake go through
+that genome's neat.nn.FeedForwardNetwork, and the argmax of the outputs is the
+action (train_dqn.py:725-772, HybridNEATEnemy, is the same head in battle
+mode). GenomeHeads is that head for a whole batch, a different network per env,
+through snake_genome_actions (marl-snake_amd/csrc/genome_kernels.hip; the exact
+semantics are in include/snake_env.h); evaluate_population() is the vector form
+of eval_genomes.
+
+The arithmetic is numpy 1.21's, the version the reference pins: there a float32
+feature times a Python float weight is a float64 product, so the features are
+widened to float64 and everything else is float64 (under numpy 2 the same line
+would compute in float32).
+"""
+import ctypes
+
+import numpy as np
+
+from ._native import GenomeCfg, GenomeLayout, GenomeProg, GenomeTile, check, lib
+
+RELU, SIGMOID, TANH = 0, 1, 2       # SNAKE_GENOME_RELU / _SIGMOID / _TANH
+_ACT = {'relu_activation': RELU, 'relu': RELU, 'sigmoid_activation': SIGMOID, 'sigmoid': SIGMOID,
+        'tanh_activation': TANH, 'tanh': TANH}
+_AGG = ('sum_aggregation', 'sum')
+_FIELDS = ('node_off', 'node_act', 'node_bias', 'node_resp', 'link_off', 'link_src', 'link_w', 'out_slot')
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def _name(f):
+    return f if isinstance(f, str) else getattr(f, '__name__', repr(f))
+
+
+class LinearNetwork:
+    """What FeedForwardNetwork.create leaves behind for the genome of
+    fc3_to_genome (train_ga.py:199-215): inputs -1 .. -I, outputs 0 .. A-1 (the
+    keys of neat-python's config), one node per output with the links in input
+    order, response 1 and the sum aggregation."""
+
+    def __init__(self, weight, bias, activation='relu'):
+        weight, bias = np.asarray(weight), np.asarray(bias)
+        if weight.ndim != 2 or bias.shape != (weight.shape[0],):
+            raise ValueError('weight must be (A, I) and bias (A,) (got %s and %s)' % (weight.shape, bias.shape))
+        A, I = weight.shape
+        self.input_nodes = [-i - 1 for i in range(I)]
+        self.output_nodes = list(range(A))
+        self.node_evals = [(o, activation, 'sum', float(bias[o]), 1.0,
+                            [(self.input_nodes[i], float(weight[o, i])) for i in range(I)]) for o in range(A)]
+
+
+def pack(networks, num_inputs=128):
+    """The flat program of a list of networks (objects with input_nodes,
+    output_nodes and node_evals, e.g. neat.nn.FeedForwardNetwork): a dict of
+    numpy arrays, the fields of snake_genome_prog (include/snake_env.h).
+
+    Slots 0 .. I-1 are the inputs and slot I + k is the k-th entry of
+    node_evals, so a link points at a lower slot. A link whose source is an
+    output key that nothing has evaluated yet reads activate()'s initial 0.0:
+    its product is a zero and leaves the sum as it is, so it is dropped."""
+    networks = list(networks)
+    if not networks:
+        raise ValueError('GenomeHeads needs at least one network')
+    I = int(num_inputs)
+    A = len(networks[0].output_nodes)
+    node_off, node_act, node_bias, node_resp = [0], [], [], []
+    link_off, link_src, link_w, out_slot = [0], [], [], []
+    for gi, net in enumerate(networks):
+        if len(net.input_nodes) != I:
+            raise ValueError('network %d has %d inputs, not %d' % (gi, len(net.input_nodes), I))
+        if len(net.output_nodes) != A:
+            raise ValueError('network %d has %d outputs, network 0 has %d' % (gi, len(net.output_nodes), A))
+        slot = {k: i for i, k in enumerate(net.input_nodes)}
+        zero = set(net.output_nodes) - set(slot)        # (output keys still at their initial 0.0)
+        for k, (node, act, agg, bias, response, links) in enumerate(net.node_evals):
+            if _name(act) not in _ACT:
+                raise ValueError('network %d node %r: activation %s is not one of relu, sigmoid, tanh'
+                                 % (gi, node, _name(act)))
+            if _name(agg) not in _AGG:
+                raise ValueError('network %d node %r: aggregation %s is not sum' % (gi, node, _name(agg)))
+            for src, w in links:
+                if src in slot:
+                    link_src.append(slot[src])
+                    link_w.append(float(w))
+                elif src not in zero:
+                    raise ValueError('network %d node %r: link from %r, which has no value' % (gi, node, src))
+            link_off.append(len(link_src))
+            node_act.append(_ACT[_name(act)])
+            node_bias.append(float(bias))
+            node_resp.append(float(response))
+            slot[node] = I + k
+            zero.discard(node)
+        node_off.append(len(node_act))
+        out_slot.append([slot.get(k, -1) for k in net.output_nodes])
+    if len(link_src) > 2 ** 30 or len(node_act) > 2 ** 30:
+        raise ValueError('the population has more than 2^30 nodes or links')
+    return dict(node_off=np.asarray(node_off, np.int32), node_act=np.asarray(node_act, np.int32),
+                node_bias=np.asarray(node_bias, np.float64), node_resp=np.asarray(node_resp, np.float64),
+                link_off=np.asarray(link_off, np.int32), link_src=np.asarray(link_src, np.int32),
+                link_w=np.asarray(link_w, np.float64), out_slot=np.asarray(out_slot, np.int32).reshape(len(networks), A))
+
+
+def program_cfg(prog, num_inputs):
+    """The snake_genome_cfg of a packed program."""
+    G, A = prog['out_slot'].shape
+    sizes = np.diff(prog['node_off'].astype(np.int64))
+    return GenomeCfg(int(num_inputs), int(A), int(G), int(sizes.max()) if sizes.size else 0,
+                     int(prog['node_act'].size), int(prog['link_src'].size))
+
+
+def check_program(prog, cfg, L=None):
+    """snake_genome_check on host arrays: ValueError naming the field when an
+    offset, activation id, link source or output slot is out of range."""
+    L = L or lib()
+    arrs = {k: np.ascontiguousarray(prog[k]) for k in _FIELDS}
+    for k in _FIELDS:
+        want = np.float64 if k in ('node_bias', 'node_resp', 'link_w') else np.int32
+        if arrs[k].dtype != want:
+            raise TypeError('%s must be %s (got %s)' % (k, np.dtype(want), arrs[k].dtype))
+    G, A, n, m = cfg.num_genomes, cfg.num_outputs, cfg.num_nodes, cfg.num_links
+    sizes = dict(node_off=G + 1, node_act=n, node_bias=n, node_resp=n, link_off=n + 1, link_src=m, link_w=m,
+                 out_slot=G * A)
+    for k in _FIELDS:           # (the C call reads exactly these many elements)
+        if arrs[k].size != sizes[k]:
+            raise ValueError('%s has %d elements, the cfg says %d' % (k, arrs[k].size, sizes[k]))
+    p = GenomeProg(*(arrs[k].ctypes.data_as(ctypes.c_void_p) for k in _FIELDS))
+    check(L.snake_genome_check(ctypes.byref(cfg), ctypes.byref(p)), L)
+
+
+class GenomeHeads:
+    """activate() + argmax for (N, S) snakes at once, env i with its own genome.
+
+    networks: objects with input_nodes, output_nodes and node_evals = [(node,
+    activation, aggregation, bias, response, [(source, weight), ...]), ...]; a
+    neat.nn.FeedForwardNetwork works unchanged. Activations and aggregations are
+    recognised by __name__ (relu_activation, sigmoid_activation,
+    tanh_activation, sum_aggregation) or given as 'relu', 'sigmoid', 'tanh',
+    'sum'; anything else raises ValueError, as does a genome that fails
+    snake_genome_check. genome_of_env: the genome index of each env (default:
+    env i runs genome i); a genome may serve several envs, in any order."""
+
+    def __init__(self, networks, num_inputs=128, genome_of_env=None, device=None, lib_path=None):
+        self._L = L = lib(lib_path)
+        self.program = pack(networks, num_inputs)
+        self.cfg = program_cfg(self.program, num_inputs)
+        check(L.snake_genome_plan(ctypes.byref(self.cfg), 0, None), L)     # ValueError before any device work
+        check_program(self.program, self.cfg, L)
+        self.num_inputs, self.num_outputs, self.num_genomes = self.cfg.num_inputs, self.cfg.num_outputs, self.cfg.num_genomes
+        g = np.arange(self.num_genomes) if genome_of_env is None else np.asarray(genome_of_env)
+        if g.ndim != 1 or g.size == 0 or not np.issubdtype(g.dtype, np.integer):
+            raise ValueError('genome_of_env must be a list of genome indices, one per env')
+        if g.min() < 0 or g.max() >= self.num_genomes:
+            raise ValueError('genome_of_env must stay in [0, %d)' % self.num_genomes)
+        self.genome_of_env = np.ascontiguousarray(g, np.int32)
+        self.num_envs = int(g.size)
+        self.device = _torch().device(device) if device is not None else None   # None: the first features'
+        self._dev_prog = None
+        self._plans = {}        # S -> (layout, tiles, rows, scratch) on the device
+
+    @classmethod
+    def from_linear(cls, weight, bias, activation='relu', num_envs=1, **kw):
+        """The head of fc3_to_genome (train_ga.py:199-215) for every env of a
+        batch: output o is act(bias[o] + sum_i x_i * weight[o, i]), the sum in
+        input order. weight (A, I) and bias (A,): arrays or tensors; num_envs:
+        the envs of the batch, which all run this one genome."""
+        def host(t):
+            return t.detach().cpu().numpy() if hasattr(t, 'detach') else np.asarray(t)
+        weight, bias = host(weight), host(bias)
+        net = LinearNetwork(weight, bias, activation)
+        kw.setdefault('genome_of_env', [0] * int(num_envs))
+        return cls([net], num_inputs=weight.shape[1], **kw)
+
+    def tiles(self, num_snakes):
+        """(layout, tiles (T, 4) int32, rows (N*S,) int32) on the host: snake_genome_tiles."""
+        L, S = self._L, int(num_snakes)
+        lay = GenomeLayout()
+        check(L.snake_genome_plan(ctypes.byref(self.cfg), self.num_envs * S, ctypes.byref(lay)), L)
+        rows = np.empty(self.num_envs * S, np.int32)
+        tiles = np.empty((max(int(lay.max_tiles), 1), 4), np.int32)
+        assert tiles.itemsize * 4 == ctypes.sizeof(GenomeTile)
+        P = ctypes.c_void_p
+        n = check(L.snake_genome_tiles(ctypes.byref(self.cfg), self.program['node_off'].ctypes.data_as(P),
+                                       self.genome_of_env.ctypes.data_as(P), self.num_envs, S,
+                                       rows.ctypes.data_as(P), tiles.ctypes.data_as(P), tiles.shape[0]), L)
+        return lay, tiles[:n].copy(), rows
+
+    def _upload(self, dev):
+        torch = _torch()
+        self._dev_arrays = {k: torch.from_numpy(np.ascontiguousarray(self.program[k])).to(dev) for k in _FIELDS}
+        self._dev_prog = GenomeProg(*(ctypes.c_void_p(self._dev_arrays[k].data_ptr()) if self._dev_arrays[k].numel()
+                                      else None for k in _FIELDS))
+
+    def __call__(self, features, skip=None, return_outputs=False):
+        """features: contiguous float32 (N*S, I) or (N, S, I) on the GPU; skip:
+        (N, S) bool/uint8 or None -- snakes that get action 0. Returns the
+        actions, int8 (N, S), ready for SnakeVecEnv.step; with return_outputs
+        also the networks' outputs, float64 (N, S, A)."""
+        torch = _torch()
+        N, I, A = self.num_envs, self.num_inputs, self.num_outputs
+        if not isinstance(features, torch.Tensor) or features.dtype != torch.float32:
+            raise TypeError('GenomeHeads takes the features as a float32 tensor')
+        if features.shape[-1] != I or features.numel() % (N * I) or features.numel() == 0:
+            raise ValueError('features shape %s is not (%d * S, %d)' % (tuple(features.shape), N, I))
+        S = features.numel() // (N * I)
+        if features.dim() not in (2, 3) or (features.dim() == 3 and features.shape[0] != N):
+            raise ValueError('features shape %s is neither (%d, %d) nor (%d, %d, %d)'
+                             % (tuple(features.shape), N * S, I, N, S, I))
+        dev = features.device
+        if dev.type != 'cuda':
+            raise ValueError('GenomeHeads needs the features on the GPU (got %s); there is no CPU fallback' % dev)
+        if self.device is None or (self.device.type == 'cuda' and self.device.index is None):
+            self.device = dev
+        if dev != self.device:
+            raise ValueError('features are on %s, this GenomeHeads on %s' % (dev, self.device))
+        features = features.contiguous()
+        if self._dev_prog is None:
+            self._upload(dev)
+        if S not in self._plans:
+            lay, tiles, rows = self.tiles(S)
+            scratch = torch.empty(int(lay.scratch), dtype=torch.uint8, device=dev) if lay.scratch else None
+            self._plans[S] = (lay, torch.from_numpy(tiles).to(dev), torch.from_numpy(rows).to(dev), scratch)
+        lay, tiles, rows, scratch = self._plans[S]
+        if skip is not None:
+            skip = torch.as_tensor(skip, device=dev).reshape(N, S).to(torch.uint8).contiguous()
+        actions = torch.empty((N, S), dtype=torch.int8, device=dev)
+        outputs = torch.empty((N, S, A), dtype=torch.float64, device=dev) if return_outputs else None
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        P = ctypes.c_void_p
+        with torch.cuda.device(dev):
+            check(self._L.snake_genome_actions(
+                ctypes.byref(self.cfg), ctypes.byref(self._dev_prog), P(tiles.data_ptr()), P(rows.data_ptr()),
+                tiles.shape[0], P(features.data_ptr()), P(skip.data_ptr()) if skip is not None else None,
+                P(actions.data_ptr()), P(outputs.data_ptr()) if outputs is not None else None,
+                P(scratch.data_ptr()) if scratch is not None else None, N * S, stream), self._L)
+        self._keep = (features, skip)
+        return (actions, outputs) if return_outputs else actions
+
+
+def population_fitness(R, genome_of_env, num_genomes):
+    """(fitness (N,), genome_fitness (G,)) of the summed rewards R (N, S):
+    np.mean of each env's row, taken on a contiguous (S,) array as the reference
+    does (train_ga.py:241), and per genome the mean over its envs (nan: none)."""
+    R = np.asarray(R, np.float64)
+    fitness = np.array([np.mean(np.ascontiguousarray(R[i])) for i in range(R.shape[0])], np.float64)
+    genome_of_env = np.asarray(genome_of_env)
+    genome_fitness = np.full(int(num_genomes), np.nan)
+    for g in np.unique(genome_of_env):
+        genome_fitness[g] = np.mean(fitness[genome_of_env == g])
+    return fitness, genome_fitness
+
+
+def evaluate_population(env, features, heads, steps=512, sync_every=32):
+    """The vector form of eval_genomes (train_ga.py:224-257): env i of `env` (a
+    SnakeVecEnv) plays one episode under genome heads.genome_of_env[i].
+
+    features: any callable from uint8 (N*S, h, w, c) observations to float32
+    (N*S, I), e.g. DQNForward(...).forward_features. The env is reset; at every
+    step the features go through the heads with skip = done & ~episode_done[:,
+    None] of the step before (a dead snake gets action 0, :236), and R (N, S)
+    float64 takes one `R += rew` per step, as in the reference, while the env's
+    first episode lasts. From the step that ends it the env's R is frozen and
+    its snakes are skipped (the env itself restarts and idles). The loop ends
+    after `steps` steps, or at a multiple of sync_every steps at which every env
+    has finished -- the only host sync, which does not change the results.
+
+    Returns (R, fitness, genome_fitness): R as a numpy array, fitness[i] =
+    np.mean(R[i]), computed by numpy on the host so that it is the reference's
+    float(R.mean()) bit for bit, and genome_fitness[g] the mean of fitness over
+    the envs of genome g (nan for a genome without an env).
+
+    Two deviations from the reference: it draws every genome's episodes from one
+    global numpy stream, here env i has its own seed (seed + i); and an episode
+    ends by the env's own rule, its max_episode_steps included."""
+    torch = _torch()
+    N = env.num_envs
+    S, h, w, c = env.obs_shape
+    if heads.num_envs != N:
+        raise ValueError('heads serve %d envs, the env has %d' % (heads.num_envs, N))
+    obs = env.reset()
+    R = torch.zeros((N, S), dtype=torch.float64, device=env.device)
+    finished = torch.zeros(N, dtype=torch.bool, device=env.device)
+    skip = None
+    for t in range(int(steps)):
+        actions = heads(features(obs.view(N * S, h, w, c)), skip=skip)
+        obs, rew, done, info = env.step(actions)
+        R = torch.where(finished[:, None], R, R + rew)
+        ended = info['episode_done']
+        finished = finished | ended
+        skip = (done & ~ended[:, None]) | finished[:, None]
+        if (t + 1) % int(sync_every) == 0 and bool(finished.all()):
+            break
+    R = R.cpu().numpy()
+    return (R,) + population_fitness(R, heads.genome_of_env, heads.num_genomes)
