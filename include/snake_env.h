@@ -356,6 +356,37 @@ int snake_safe_actions(const snake_policy_cfg *cfg, const uint8_t *obs, const fl
                        const uint8_t *skip, int8_t *dirs, int8_t *actions, int64_t num_envs,
                        void *stream);
 
+/* ---- Greedy opponent: the rule-based fruit seeker of the reference's battle
+ * mode (train_dqn.py:774-856 GreedyEnemy.get_action) for every snake at once,
+ * each snake on its own observation alone (no claimed cells, no order among
+ * the snakes). cfg is a snake_policy_cfg with the limits of snake_policy_plan;
+ * fill_limit is validated but not used. A snake whose skip byte is nonzero
+ * gets action 0 and keeps its direction. Otherwise its head is the first
+ * row-major cell with channel 5 == 1; without one the action is 0 and the
+ * direction stays as it is (unknown stays unknown). The target fruit is the
+ * cell with channel 1 == 1 nearest to the head by |y-hy| + |x-hx|, the first
+ * in row-major order among equals; there may be none. An unknown direction is
+ * read off the head's neighbours in the order (-1,0), (1,0), (0,-1), (0,1):
+ * the first one inside the map with channel 6 == 1 or channel 7 == 1 gives
+ * direction = head - that cell; none gives (-1,0). (The evaluator's rule above
+ * asks the neighbours in another order.) The moves are {0: (dy,dx), 1:
+ * (-dx,dy), 2: (dx,-dy)}; a move is dead when its cell is outside the map or
+ * has channel 0, 2, 3, 4, 6 or 7 == 1; a live move scores -(|y-fy| + |x-fx|)
+ * from its cell to the target fruit, 0 without a fruit. All three dead: action
+ * 0, the direction becomes move 0 (so a direction read off the body is
+ * stored), rnd is not read. Otherwise, with best[] the n live moves of maximal
+ * score in ascending order and u the snake's 32 random bits, the action is
+ * best[((uint64_t)u * n) >> 32] and the direction becomes that move. The
+ * reference draws with random.choice; here the random bits come in, so the
+ * call is a pure function of its arguments.
+ *
+ * obs, skip, dirs, actions: as in snake_safe_actions; rnd: uint32 [N][S] or
+ * NULL (all zero: the first best move). One launch (k_greedy) on `stream`, on
+ * the stream's device. */
+int snake_greedy_actions(const snake_policy_cfg *cfg, const uint8_t *obs, const uint32_t *rnd,
+                         const uint8_t *skip, int8_t *dirs, int8_t *actions,
+                         int64_t num_envs, void *stream);
+
 /* ---- Replay buffer: the reference trainer's deque of transitions
  * (train_dqn.py:89-100 ReplayBuffer, filled at :290-298, sampled at :228-240)
  * as rings in device memory, filled straight from one env step's tensors.

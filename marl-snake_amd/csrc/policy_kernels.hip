@@ -61,14 +61,6 @@ struct Rec {
     int masked;             // bit a: move a is masked by the snake's own observation
 };
 
-// 0x80 in every byte of x that equals 1 (exact per byte: no carry crosses a byte)
-__device__ __forceinline__ uint32_t bytes_eq1(uint32_t x)
-{
-    const uint32_t y = x ^ 0x01010101u;
-    const uint32_t t = (y & 0x7f7f7f7fu) + 0x7f7f7f7fu;
-    return ~(t | y | 0x7f7f7f7fu);
-}
-
 // the six flag bits of one cell: lo = channels 0-3, hi = channels 4-7
 __device__ __forceinline__ uint32_t cell_flags(uint32_t lo, uint32_t hi)
 {

@@ -11,6 +11,7 @@ from .dqn import DQNForward  # noqa: F401
 from .policy import SafeActions, evaluate  # noqa: F401
 from .replay import Collector, ReplayBuffer  # noqa: F401
 from .neat_head import GenomeHeads, evaluate_population  # noqa: F401
+from .arena import GreedyActions, HybridNEAT, SafeDQN, battle  # noqa: F401
 from .wrappers import RenderGUI, SingleAgent, SingleAgentVec, SingleMultiAgent, make_snake  # noqa: F401
 
 __version__ = '0.1.0'

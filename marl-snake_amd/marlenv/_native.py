@@ -16,7 +16,7 @@ SNAKE_ABI_VERSION = 19
 EXPORTS = ('snake_plan', 'snake_build_candidates', 'snake_seed', 'snake_reset', 'snake_step',
            'snake_sync', 'snake_release', 'snake_render_rgb', 'snake_timing_enable', 'snake_timing_read', 'snake_debug_set', 'snake_last_error', 'snake_abi_version',
            'snake_dqn_plan', 'snake_dqn_rows', 'snake_dqn_forward', 'snake_dqn32_scratch', 'snake_dqn32_forward',
-           'snake_policy_plan', 'snake_safe_actions',
+           'snake_policy_plan', 'snake_safe_actions', 'snake_greedy_actions',
            'snake_replay_plan', 'snake_replay_push', 'snake_replay_gather',
            'snake_genome_plan', 'snake_genome_check', 'snake_genome_tiles', 'snake_genome_actions')
 
@@ -160,6 +160,7 @@ def lib(path=None):
     L.snake_dqn32_forward.argtypes = [ctypes.POINTER(DqnCfg), ctypes.POINTER(Dqn32Net), P, I64, P, P, P, P]
     L.snake_policy_plan.argtypes = [ctypes.POINTER(PolicyCfg)]
     L.snake_safe_actions.argtypes = [ctypes.POINTER(PolicyCfg), P, P, P, P, P, I64, P]
+    L.snake_greedy_actions.argtypes = [ctypes.POINTER(PolicyCfg), P, P, P, P, P, I64, P]
     L.snake_replay_plan.argtypes = [ctypes.POINTER(ReplayCfg), I64, ctypes.POINTER(ReplayLayout)]
     L.snake_replay_push.argtypes = [ctypes.POINTER(ReplayCfg), ctypes.POINTER(ReplayRings), P, P, P, P, P, P, P,
                                     I64, P, P]

@@ -1,0 +1,244 @@
+"""Battle mode on the GPU: the snakes of one env under different policies.
+
+train_dqn.py's `--mode battle` (BattleArena.run_battle, train_dqn.py:858-960)
+is the one place in the reference where the snakes of an env are driven by
+different policies: slot 0 by the DQN behind the safe-action rule, the others
+by external agents, among them HybridNEATEnemy (:725-772) and GreedyEnemy
+(:774-856). GreedyActions is GreedyEnemy.get_action for a whole batch, through
+snake_greedy_actions (marl-snake_amd/csrc/greedy_kernels.hip; the exact
+semantics are in include/snake_env.h); SafeDQN and HybridNEAT put SafeActions
+and GenomeHeads behind the controller protocol below, and battle() is the
+vector form of run_battle with results per snake slot.
+
+The controller protocol: a controller is a callable
+
+    ctrl(obs, skip, slots=slots) -> int8 (N, S)
+
+obs is the env's uint8 (N, S, h, w, c) tensor; skip (N, S) bool marks the
+snakes the controller must not drive (done, or owned by another controller),
+and it returns 0 there; slots is the tuple of snake indices it owns. It may
+offer forget(ended), called with info['episode_done'] after every step. Any
+plain callable of that shape fits, e.g. a PPO actor (the reference's battle
+has one, whose code it does not ship).
+"""
+import ctypes
+
+import numpy as np
+
+from ._native import PolicyCfg, check, lib
+from .policy import DIR_UNKNOWN, SafeActions
+
+
+def _torch():
+    import torch
+    return torch
+
+
+class GreedyActions:
+    """GreedyEnemy.get_action for (N, S) snakes at once, each on its own
+    observation: head for the nearest fruit by a move that does not die, ties
+    broken by 32 random bits per snake.
+
+    obs_shape: (S, h, w, 8), a SnakeVecEnv's obs_shape (frame_stack 1, h and w
+    at most 64, at most 16 snakes; anything else raises ValueError).
+    generator: the torch.Generator (on the GPU) the random bits are drawn from
+    when a call gets none (None: the device's default generator).
+    forget_on_reset: the reference never clears GreedyEnemy.current_direction
+    between episodes, so the first move of an episode takes the last heading of
+    the one before; False reproduces that (forget() does nothing), the default
+    starts every episode with unknown directions."""
+
+    def __init__(self, obs_shape, generator=None, forget_on_reset=True, device=None, lib_path=None):
+        if len(obs_shape) != 4:
+            raise ValueError('obs_shape must be (S, h, w, 8) (got %r)' % (tuple(obs_shape),))
+        S, h, w, c = (int(v) for v in obs_shape)
+        self._L = L = lib(lib_path)
+        self.cfg = PolicyCfg(h, w, c, S, 1)     # (fill_limit: validated, not used)
+        check(L.snake_policy_plan(ctypes.byref(self.cfg)), L)      # ValueError before any device work
+        self.obs_shape = (S, h, w, c)
+        self.generator = generator
+        self.forget_on_reset = bool(forget_on_reset)
+        self.device = _torch().device(device) if device is not None else None   # None: the first obs's
+        self.dirs = None        # (N, S, 2) int8 (dy, dx), kept across calls when none are passed
+
+    def __call__(self, obs, skip=None, dirs=None, rnd=None, slots=None):
+        """obs: contiguous uint8 (N, S, h, w, 8); skip: (N, S) bool/uint8 or None
+        -- snakes that get action 0 and keep their direction; dirs: int8 (N, S,
+        2), read and updated in place (None: this object's own tensor, all
+        unknown at first); rnd: int32 (N, S), the 32 random bits of each snake
+        (None: drawn from the generator on the device, without a host sync);
+        slots: ignored (the controller protocol's). Returns the actions, int8
+        (N, S), ready for SnakeVecEnv.step."""
+        torch = _torch()
+        S = self.obs_shape[0]
+        if obs.dtype != torch.uint8 or not obs.is_contiguous():
+            raise TypeError('GreedyActions takes the observations as a contiguous uint8 tensor')
+        if obs.dim() != 5 or tuple(obs.shape[1:]) != self.obs_shape:
+            raise ValueError('obs shape %s is not (N,) + %s' % (tuple(obs.shape), self.obs_shape))
+        dev = obs.device
+        if dev.type != 'cuda':
+            raise ValueError('GreedyActions needs the observations on the GPU (got %s); there is no CPU fallback' % dev)
+        if self.device is None or (self.device.type == 'cuda' and self.device.index is None):
+            self.device = dev
+        if dev != self.device:
+            raise ValueError('obs is on %s, this GreedyActions on %s' % (dev, self.device))
+        N = obs.shape[0]
+        if rnd is not None and (rnd.dtype != torch.int32 or tuple(rnd.shape) != (N, S) or not rnd.is_contiguous()
+                                or rnd.device != dev):
+            raise TypeError('rnd must be a contiguous int32 (N, S) tensor on %s' % dev)
+        if dirs is not None and (dirs.dtype != torch.int8 or tuple(dirs.shape) != (N, S, 2)
+                                 or not dirs.is_contiguous() or dirs.device != dev):
+            raise TypeError('dirs must be a contiguous int8 (N, S, 2) tensor on %s' % dev)
+        if skip is not None:
+            skip = torch.as_tensor(skip, device=dev).reshape(N, S).to(torch.uint8).contiguous()
+        if rnd is None:
+            rnd = torch.randint(-2 ** 31, 2 ** 31, (N, S), dtype=torch.int32, device=dev, generator=self.generator)
+        if dirs is None:
+            if self.dirs is None or self.dirs.shape[0] != N:
+                self.dirs = torch.full((N, S, 2), DIR_UNKNOWN, dtype=torch.int8, device=dev)
+            dirs = self.dirs
+        actions = torch.empty((N, S), dtype=torch.int8, device=dev)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        P = ctypes.c_void_p
+        with torch.cuda.device(dev):
+            check(self._L.snake_greedy_actions(ctypes.byref(self.cfg), P(obs.data_ptr()), P(rnd.data_ptr()),
+                                               P(skip.data_ptr()) if skip is not None else None,
+                                               P(dirs.data_ptr()), P(actions.data_ptr()), N, stream), self._L)
+        self._keep = (obs, rnd, skip)
+        return actions
+
+    def forget(self, mask):
+        """Directions of the envs where mask (N,) is True become unknown (an
+        episode ended); nothing with forget_on_reset=False."""
+        if self.forget_on_reset and self.dirs is not None:
+            torch = _torch()
+            m = torch.as_tensor(mask, device=self.dirs.device).to(torch.bool).reshape(-1, 1, 1)
+            self.dirs.masked_fill_(m, DIR_UNKNOWN)
+
+
+class _OnSlots:
+    """A controller that runs a net on the observations of its own slots alone."""
+
+    def __init__(self):
+        self._idx = {}          # (slots, device) -> int64 index tensor: uploaded once, not once per step
+
+    def _on_slots(self, fn, obs, slots, width):
+        """fn on the observations of the snakes `slots`, scattered into a zero
+        float32 (N, S, width)."""
+        torch = _torch()
+        N, S = obs.shape[:2]
+        slots = tuple(int(s) for s in slots)
+        if slots == tuple(range(S)):
+            return fn(obs.view(N * S, *obs.shape[2:])).view(N, S, width)
+        key = (slots, obs.device)
+        if key not in self._idx:
+            self._idx[key] = torch.as_tensor(slots, dtype=torch.int64, device=obs.device)
+        idx = self._idx[key]
+        sub = fn(obs.index_select(1, idx).view(N * len(slots), *obs.shape[2:]))
+        out = torch.zeros((N, S, width), dtype=torch.float32, device=obs.device)
+        out.index_copy_(1, idx, sub.view(N, len(slots), width).to(torch.float32))
+        return out
+
+
+class SafeDQN(_OnSlots):
+    """The battle's slot 0: a DQN behind the safe-action rule, as a controller.
+
+    qnet: any callable from uint8 (B, h, w, 8) observations to float32 (B, 3),
+    e.g. DQNForward(..., precision='fp32'); it runs on the observations of the
+    controller's own slots only. With several slots the rule's claimed cells
+    apply among them, in slot order, as in the evaluator; with one slot the set
+    is empty, which is what BattleArena passes (train_dqn.py:925)."""
+
+    def __init__(self, qnet, obs_shape, fill_limit=60, device=None, lib_path=None):
+        super().__init__()
+        self.qnet = qnet
+        self.policy = SafeActions(obs_shape, fill_limit=fill_limit, device=device, lib_path=lib_path)
+
+    def __call__(self, obs, skip, slots):
+        return self.policy(obs, self._on_slots(self.qnet, obs, slots, 3), skip=skip)
+
+    def forget(self, ended):
+        self.policy.forget(ended)
+
+
+class HybridNEAT(_OnSlots):
+    """HybridNEATEnemy (train_dqn.py:725-772) as a controller: `features` (a
+    callable from uint8 (B, h, w, 8) observations to float32 (B, I), e.g.
+    DQNForward(...).forward_features) on the controller's own slots, then
+    `heads`, a GenomeHeads over the env's N envs. One genome for all of them is
+    GenomeHeads(..., genome_of_env=[0] * N) or GenomeHeads.from_linear."""
+
+    def __init__(self, features, heads):
+        super().__init__()
+        self.features, self.heads = features, heads
+
+    def __call__(self, obs, skip, slots):
+        return self.heads(self._on_slots(self.features, obs, slots, self.heads.num_inputs), skip=skip)
+
+
+def battle(env, controllers, steps):
+    """The vector form of BattleArena.run_battle (train_dqn.py:870-960): steps
+    `env` (a SnakeVecEnv with all-done auto-reset) `steps` times, snake slot s
+    of every env driven by controllers[s] (the module docstring's protocol).
+
+    controllers: one entry per snake slot; the same object may sit in several
+    slots and is then called once per step for all of them, with skip = the
+    snakes that were done before the step | the slots that are not its own. A
+    done snake gets action 0 until its env's episode ends (:920-921). After
+    every step each controller's forget(info['episode_done']), where it has
+    one, is called.
+
+    Returns (episodes, mean_reward, mean_lifetime): the episodes that finished
+    and, over them, float64 arrays of length S -- per slot the mean of the
+    episode's summed rewards (the reference's ep_rewards, :936-937) and of the
+    number of steps at whose start the snake was not done (ep_lifetimes, :923);
+    nan when no episode finished. An episode ends by the env's own rule, its
+    max_episode_steps included, not by the reference's cap of 512 steps per
+    episode. Everything is accumulated on the device; the only host sync is the
+    read of the results after the loop."""
+    torch = _torch()
+    N, S = env.num_envs, env.num_snakes
+    controllers = list(controllers)
+    if len(controllers) != S:
+        raise ValueError('battle needs one controller per snake slot: %d, not %d' % (S, len(controllers)))
+    dev = env.device
+    owners = []             # (controller, its slots, (S,) bool: not its slots), distinct objects in slot order
+    for s, c in enumerate(controllers):
+        if not any(c is o[0] for o in owners):
+            slots = tuple(i for i in range(S) if controllers[i] is c)
+            other = torch.ones(S, dtype=torch.bool, device=dev)
+            other[list(slots)] = False
+            owners.append((c, slots, other))
+    obs = env.reset()
+    for c, _, _ in owners:
+        if hasattr(c, 'forget'):
+            c.forget(torch.ones(N, dtype=torch.bool, device=dev))
+    done = torch.zeros((N, S), dtype=torch.bool, device=dev)
+    ep_reward = torch.zeros((N, S), dtype=torch.float64, device=dev)
+    ep_life = torch.zeros((N, S), dtype=torch.int64, device=dev)
+    episodes = torch.zeros((), dtype=torch.int64, device=dev)
+    reward = torch.zeros(S, dtype=torch.float64, device=dev)
+    life = torch.zeros(S, dtype=torch.int64, device=dev)
+    for _ in range(int(steps)):
+        actions = torch.zeros((N, S), dtype=torch.int8, device=dev)
+        for c, slots, other in owners:
+            a = c(obs, done | other, slots=slots)
+            actions = torch.where(other, actions, a.to(torch.int8))
+        ep_life += ~done
+        obs, rew, done, info = env.step(actions)
+        ep_reward += rew
+        ended = info['episode_done']
+        e = ended[:, None]
+        episodes += ended.sum()
+        reward += torch.where(e, ep_reward, torch.zeros_like(ep_reward)).sum(0)
+        life += torch.where(e, ep_life, torch.zeros_like(ep_life)).sum(0)
+        ep_reward = torch.where(e, torch.zeros_like(ep_reward), ep_reward)
+        ep_life = torch.where(e, torch.zeros_like(ep_life), ep_life)
+        done = done & ~e
+        for c, _, _ in owners:
+            if hasattr(c, 'forget'):
+                c.forget(ended)
+    n = int(episodes)
+    if n == 0:
+        return 0, np.full(S, np.nan), np.full(S, np.nan)
+    return n, reward.cpu().numpy() / n, life.cpu().numpy().astype(np.float64) / n
