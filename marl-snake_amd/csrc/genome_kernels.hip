@@ -391,10 +391,5 @@ extern "C" int snake_genome_actions(const snake_genome_cfg *cfg, const snake_gen
     DeviceGuard dg(s);
     if (dg.dev < 0) return SNAKE_E_LAUNCH;
     hipLaunchKernelGGL(genome::k_genome_actions, dim3((unsigned)num_tiles), dim3(64), (size_t)lay.lds_bytes, s, g);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        set_error("k_genome_actions launch failed: %s", hipGetErrorString(err));
-        return SNAKE_E_LAUNCH;
-    }
-    return SNAKE_OK;
+    return launch_status("k_genome_actions");
 }

@@ -8,14 +8,11 @@
 //   G = 1: rows on 64 lanes, any h <= 64.
 //   G = 4: four snakes per wave for h <= 16.
 //
-//  1. The wave's snakes are contiguous in memory: their G*h*w cells (8 bytes
-//     each) are read as one string with 16-byte loads, two cells per lane and
-//     128 cells per pass, as in k_safe_actions (policy_kernels.hip). Each cell
-//     becomes four flag bits (channel == 1 tests); two lane exchanges put cell
-//     p of the pass on lane p % 64, so one __ballot per flag and half-pass is a
-//     64-bit piece of that flag's bit string. The pieces go to LDS; every lane
-//     then cuts its row out of each string at (l / R) * h*w + (l % R) * w: four
-//     w-bit row words (deadly, fruit, my head, my body|tail).
+//  1. The wave's snakes are contiguous in memory: their G*h*w cells go through
+//     the front end of obs_rows.h as one string of four flag bits per cell
+//     (channel == 1 tests), and every lane cuts its row out of each string at
+//     (l / R) * h*w + (l % R) * w: four w-bit row words (deadly, fruit, my
+//     head, my body|tail).
 //  2. Per snake, on its R lanes: the head (first row with a head bit), the
 //     direction, the nearest fruit -- in a row the only candidates are the
 //     highest fruit bit at or left of the head's column and the lowest one
@@ -32,18 +29,16 @@
 
 #include "snake_internal.h"
 #include "snake_device.h"
+#include "obs_rows.h"
 
 namespace snake {
 namespace greedy {
 
-constexpr int kMaxSide = 64;
 constexpr int kWaves = 4;          // waves per workgroup
 constexpr int kPackRows = 16;      // G = 4: a snake's rows on 16 lanes
 constexpr int kFlags = 4;
 enum { F_DEADLY = 0, F_FRUIT = 1, F_HEAD = 2, F_BODY = 3 };
-// 64-bit words of one flag's bit string: the passes' (G*h*w <= 4096 cells and
-// one cell of alignment) and the word after a row's first
-constexpr int kNw = 2 * ((kMaxSide * kMaxSide + 1 + 127) / 128) + 2;
+constexpr int kNw = flag_words(kMaxSide * kMaxSide);     // a wave has G*h*w <= 4096 cells
 
 struct Args {
     const uint8_t *obs;
@@ -90,55 +85,15 @@ __global__ void __launch_bounds__(64 * kWaves) k_greedy(const Args g)
     const int count = nsn * hw;         // the wave's cells
     uint64_t *lin = lin_all[wv];
     // ---- 1. the cells -> row words
-    const long long cell0 = first * hw, a0 = cell0 & ~1ll;   // (16-byte aligned start)
-    const int d = (int)(cell0 - a0);
-    const int passes = (count + d + 127) >> 7;
-    for (int i = 0; i < passes; i++) {
-        const long long c = a0 + (long long)i * 128 + 2 * lane;
-        const int rel = (int)(c - cell0);
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (rel < count) {
-            if (c + 1 < g.cells) v = *reinterpret_cast<const uint4 *>(g.obs + c * 8);
-            else {      // the very last cell of an odd tensor
-                const uint2 t = *reinterpret_cast<const uint2 *>(g.obs + c * 8);
-                v.x = t.x;
-                v.y = t.y;
-            }
-        }
-        const uint32_t f0 = (rel >= 0 && rel < count) ? cell_flags(v.x, v.y) : 0;
-        const uint32_t f1 = (rel + 1 < count) ? cell_flags(v.z, v.w) : 0;
-        const int pk = (int)(f0 | f1 << 8), sh = 8 * (lane & 1);
-        const uint32_t fa = (uint32_t)__shfl(pk, lane >> 1) >> sh;          // cell i*128 + lane
-        const uint32_t fb = (uint32_t)__shfl(pk, 32 + (lane >> 1)) >> sh;   // cell i*128 + 64 + lane
-#pragma unroll
-        for (int k = 0; k < kFlags; k++) {
-            const uint64_t wa = __ballot((fa >> k) & 1), wb = __ballot((fb >> k) & 1);
-            if (lane == 0) {
-                lin[k * kNw + 2 * i] = wa;
-                lin[k * kNw + 2 * i + 1] = wb;
-            }
-        }
-    }
-    // the word after the last pass: a row that ends in the last written word reads it too
-    if (lane < kFlags) lin[lane * kNw + 2 * passes] = 0;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    // the lane's row = bits [start, start + w) of each string; start < count + d
-    // <= 128 * passes, so index + 1 <= 2 * passes <= 66 < kNw: a written word or
-    // the zero after them
+    const int d = load_flag_strings<kFlags, 0>(g.obs, g.cells, first * hw, count, lin, kNw, lane, cell_flags).d;
+    // the lane's row = bits [start, start + w) of each string
     const bool has_row = grp < nsn && r < h;
     const uint64_t wmask = w == 64 ? ~0ull : (1ull << w) - 1;
     const uint64_t rowmask = has_row ? wmask : 0;
+    const int start = (has_row ? grp * hw + r * w : 0) + d;
     uint64_t m[kFlags];
-    {
-        const int start = (has_row ? grp * hw + r * w : 0) + d, idx = start >> 6, sh = start & 63;
 #pragma unroll
-        for (int k = 0; k < kFlags; k++) {
-            const uint64_t lo = lin[k * kNw + idx], hi = lin[k * kNw + idx + 1];
-            m[k] = ((lo >> sh) | (sh ? hi << (64 - sh) : 0)) & rowmask;
-        }
-    }
+    for (int k = 0; k < kFlags; k++) m[k] = cut_row(lin + k * kNw, start) & rowmask;
     // ---- 2. per snake. Every lane runs every ballot and shuffle: the branches
     // below are on values uniform over the wave or taken after the last exchange.
     auto any = [&](bool p) { return ((__ballot(p) >> gbase) & gmask) != 0; };
@@ -237,15 +192,11 @@ namespace {
 int greedy_launch(const snake_policy_cfg *cfg, const uint8_t *obs, const uint32_t *rnd, const uint8_t *skip,
                   int8_t *dirs, int8_t *actions, int64_t num_envs, void *stream, bool rows_only)
 {
-    if (int rc = snake_policy_plan(cfg)) return rc;
-    if (!obs || !dirs || !actions) { set_error("snake_greedy_actions: NULL buffer"); return SNAKE_E_ARG; }
-    if ((uintptr_t)obs & 15) { set_error("snake_greedy_actions: obs must be 16-byte aligned"); return SNAKE_E_ARG; }
+    bool nothing;
+    if (int rc = check_obs_call("snake_greedy_actions", cfg, obs, dirs, actions, num_envs, &nothing)) return rc;
+    // (after the num_envs range, where it used to come before it: a call wrong in both reports the range)
     if ((uintptr_t)rnd & 3) { set_error("snake_greedy_actions: rnd must be 4-byte aligned"); return SNAKE_E_ARG; }
-    if (num_envs < 0 || num_envs > (1ll << 26)) {
-        set_error("snake_greedy_actions: num_envs must be in [0, 2^26] (got %lld)", (long long)num_envs);
-        return SNAKE_E_ARG;
-    }
-    if (num_envs == 0) return SNAKE_OK;
+    if (nothing) return SNAKE_OK;
     greedy::Args g;
     g.obs = obs;
     g.rnd = rnd;
@@ -264,12 +215,7 @@ int greedy_launch(const snake_policy_cfg *cfg, const uint8_t *obs, const uint32_
     if (dg.dev < 0) return SNAKE_E_LAUNCH;
     if (packed) hipLaunchKernelGGL(greedy::k_greedy<4>, grid, block, 0, s, g);
     else hipLaunchKernelGGL(greedy::k_greedy<1>, grid, block, 0, s, g);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        set_error("k_greedy launch failed: %s", hipGetErrorString(err));
-        return SNAKE_E_LAUNCH;
-    }
-    return SNAKE_OK;
+    return launch_status("k_greedy");
 }
 
 }  // namespace

@@ -4,13 +4,10 @@
 //
 // k_safe_actions: one workgroup per env, one wave per snake.
 //
-//  1. The wave reads its snake's h*w cells (8 bytes each) with 16-byte loads,
-//     two cells per lane and 128 cells per pass. Each cell becomes six flag bits
-//     (channel == 1 tests); two lane exchanges put cell p of the pass on lane
-//     p % 64, so one __ballot per flag and half-pass is a 64-bit piece of that
-//     flag's row-major bit string. The pieces go to LDS; lane r then cuts row r
-//     out of each string: six w-bit row words per lane (deadly-but-tail, fruit,
-//     other head, my head, my body, my tail).
+//  1. The wave's cells are its snake's h*w; the front end of obs_rows.h turns
+//     them into six flag bits per cell (channel == 1 tests) and lane r's six
+//     w-bit row words of row r (deadly-but-tail, fruit, other head, my head, my
+//     body, my tail), and counts the snake's own cells on the way.
 //  2. Everything that depends on the snake's own observation alone: the head,
 //     the direction, the three targets, the out-of-map / deadly / beside-a-head
 //     tests, and the flood fill of the three targets as a fixpoint of
@@ -33,14 +30,15 @@
 
 #include "snake_internal.h"
 #include "snake_device.h"
+#include "obs_rows.h"
 
 namespace snake {
 namespace policy {
 
-constexpr int kMaxSide = 64;       // rows on lanes, columns on the bits of a 64-bit word
 constexpr int kMaxLimit = 4096;    // = kMaxSide^2: a larger limit never binds
 constexpr int kFlags = 6;
 enum { F_DEAD6 = 0, F_FRUIT = 1, F_OHEAD = 2, F_MYHEAD = 3, F_MYBODY = 4, F_MYTAIL = 5 };
+constexpr uint32_t kLengthFlags = 1u << F_MYHEAD | 1u << F_MYBODY | 1u << F_MYTAIL;     // the snake's own cells
 
 struct Args {
     const uint8_t *obs;
@@ -117,52 +115,16 @@ __global__ void __launch_bounds__(1024) k_safe_actions(const Args g)
     if (!skipped) {
         uint64_t *lin = lin_all + (size_t)s * kFlags * g.nw;
         // ---- 1. the cells -> row words
-        const long long cell0 = snake * hw, a0 = cell0 & ~1ll;   // (16-byte aligned start)
-        const int d = (int)(cell0 - a0);
-        const int passes = (hw + d + 127) >> 7;
-        int length = 0;
-        for (int i = 0; i < passes; i++) {
-            const long long c = a0 + (long long)i * 128 + 2 * lane;
-            const int rel = (int)(c - cell0);
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (rel < hw) {
-                if (c + 1 < g.cells) v = *reinterpret_cast<const uint4 *>(g.obs + c * 8);
-                else {      // the very last cell of an odd tensor
-                    const uint2 t = *reinterpret_cast<const uint2 *>(g.obs + c * 8);
-                    v.x = t.x;
-                    v.y = t.y;
-                }
-            }
-            const uint32_t f0 = (rel >= 0 && rel < hw) ? cell_flags(v.x, v.y) : 0;
-            const uint32_t f1 = (rel + 1 < hw) ? cell_flags(v.z, v.w) : 0;
-            const int pk = (int)(f0 | f1 << 8), sh = 8 * (lane & 1);
-            const uint32_t fa = (uint32_t)__shfl(pk, lane >> 1) >> sh;          // cell i*128 + lane
-            const uint32_t fb = (uint32_t)__shfl(pk, 32 + (lane >> 1)) >> sh;   // cell i*128 + 64 + lane
-#pragma unroll
-            for (int k = 0; k < kFlags; k++) {
-                const uint64_t wa = __ballot((fa >> k) & 1), wb = __ballot((fb >> k) & 1);
-                if (lane == 0) {
-                    lin[k * g.nw + 2 * i] = wa;
-                    lin[k * g.nw + 2 * i + 1] = wb;
-                }
-                if (k >= F_MYHEAD) length += __popcll(wa) + __popcll(wb);
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        // row r = bits [r*w + d, r*w + d + w) of each string; index + 1 <= hw/64 + 1 < nw
+        const FlagStrings fs = load_flag_strings<kFlags, kLengthFlags>(
+            g.obs, g.cells, snake * hw, hw, lin, g.nw, lane, cell_flags);
+        const int length = fs.count;
+        // row r = bits [r*w + d, r*w + d + w) of each string
         const uint64_t wmask = w == 64 ? ~0ull : (1ull << w) - 1;
         const uint64_t rowmask = lane < h ? wmask : 0;
+        const int start = (lane < h ? lane : 0) * w + fs.d;
         uint64_t m[kFlags];
-        {
-            const int start = (lane < h ? lane : 0) * w + d, idx = start >> 6, sh = start & 63;
 #pragma unroll
-            for (int k = 0; k < kFlags; k++) {
-                const uint64_t lo = lin[k * g.nw + idx], hi = lin[k * g.nw + idx + 1];
-                m[k] = ((lo >> sh) | (sh ? hi << (64 - sh) : 0)) & rowmask;
-            }
-        }
+        for (int k = 0; k < kFlags; k++) m[k] = cut_row(lin + k * g.nw, start) & rowmask;
         // ---- 2. the snake's own observation
         Rec r;
         r.state = 1;
@@ -319,13 +281,10 @@ extern "C" int snake_safe_actions(const snake_policy_cfg *cfg, const uint8_t *ob
                                   void *stream)
 {
     if (int rc = policy::check_cfg(cfg)) return rc;
-    if (!obs || !q || !dirs || !actions) { set_error("snake_safe_actions: NULL buffer"); return SNAKE_E_ARG; }
-    if ((uintptr_t)obs & 15) { set_error("snake_safe_actions: obs must be 16-byte aligned"); return SNAKE_E_ARG; }
-    if (num_envs < 0 || num_envs > (1ll << 26)) {
-        set_error("snake_safe_actions: num_envs must be in [0, 2^26] (got %lld)", (long long)num_envs);
-        return SNAKE_E_ARG;
-    }
-    if (num_envs == 0) return SNAKE_OK;
+    if (!q) { set_error("snake_safe_actions: NULL buffer"); return SNAKE_E_ARG; }     // (before obs's alignment)
+    bool nothing;
+    if (int rc = check_obs_call("snake_safe_actions", cfg, obs, dirs, actions, num_envs, &nothing)) return rc;
+    if (nothing) return SNAKE_OK;
     policy::Args g;
     g.obs = obs;
     g.q = q;
@@ -337,7 +296,7 @@ extern "C" int snake_safe_actions(const snake_policy_cfg *cfg, const uint8_t *ob
     g.w = cfg->obs_w;
     g.limit = cfg->fill_limit;
     g.cells = (long long)num_envs * g.S * g.h * g.w;
-    g.nw = 2 * ((g.h * g.w + 1 + 127) / 128) + 2;
+    g.nw = flag_words(g.h * g.w);
     g.cbits = 1;
     while ((1 << g.cbits) <= g.w) g.cbits++;
     const size_t lds = (size_t)g.S * policy::kFlags * g.nw * sizeof(uint64_t);   // at most 52 KB
@@ -345,10 +304,5 @@ extern "C" int snake_safe_actions(const snake_policy_cfg *cfg, const uint8_t *ob
     DeviceGuard dg(s);
     if (dg.dev < 0) return SNAKE_E_LAUNCH;
     hipLaunchKernelGGL(policy::k_safe_actions, dim3((unsigned)num_envs), dim3(64 * g.S), lds, s, g);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        set_error("k_safe_actions launch failed: %s", hipGetErrorString(err));
-        return SNAKE_E_LAUNCH;
-    }
-    return SNAKE_OK;
+    return launch_status("k_safe_actions");
 }

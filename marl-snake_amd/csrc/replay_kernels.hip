@@ -370,14 +370,6 @@ inline int64_t scan_blocks(int64_t N) { return (N + kScanBlock - 1) / kScanBlock
 // scratch: the header, the block offsets (a multiple of four words), the env offsets
 inline int64_t blk_words(int64_t N) { return (scan_blocks(N) + 3) / 4 * 4; }
 
-int launch_error(const char *kernel)
-{
-    const hipError_t err = hipGetLastError();
-    if (err == hipSuccess) return SNAKE_OK;
-    set_error("%s launch failed: %s", kernel, hipGetErrorString(err));
-    return SNAKE_E_LAUNCH;
-}
-
 }  // namespace replay
 }  // namespace snake
 
@@ -452,13 +444,13 @@ extern "C" int snake_replay_push(const snake_replay_cfg *cfg, const snake_replay
     DeviceGuard dg(s);
     if (dg.dev < 0) return SNAKE_E_LAUNCH;
     hipLaunchKernelGGL(replay::k_replay_count, dim3((unsigned)g.nb), dim3(replay::kScanBlock), 0, s, g);
-    if (int rc = replay::launch_error("k_replay_count")) return rc;
+    if (int rc = launch_status("k_replay_count")) return rc;
     hipLaunchKernelGGL(replay::k_replay_scan, dim3(1), dim3(replay::kScanBlock), 0, s, g);
-    if (int rc = replay::launch_error("k_replay_scan")) return rc;
+    if (int rc = launch_status("k_replay_scan")) return rc;
     const uint32_t rows_per_block = 4u << (6 - g.gshift);
     const uint32_t blocks = (g.snakes + rows_per_block - 1) / rows_per_block;
     hipLaunchKernelGGL(replay::k_replay_store, dim3(blocks), dim3(256), 0, s, g);
-    return replay::launch_error("k_replay_store");
+    return launch_status("k_replay_store");
 }
 
 extern "C" int snake_replay_gather(const snake_replay_cfg *cfg, const snake_replay_rings *rings, const int64_t *idx,
@@ -511,8 +503,8 @@ extern "C" int snake_replay_gather(const snake_replay_cfg *cfg, const snake_repl
     if (dg.dev < 0) return SNAKE_E_LAUNCH;
     if (format == SNAKE_REPLAY_U8_NHWC) {
         hipLaunchKernelGGL(replay::k_replay_gather_u8, dim3((unsigned)blocks, 2), dim3(256), 0, s, g);
-        return replay::launch_error("k_replay_gather_u8");
+        return launch_status("k_replay_gather_u8");
     }
     hipLaunchKernelGGL(replay::k_replay_gather_f32, dim3((unsigned)blocks, 2), dim3(256), 0, s, g);
-    return replay::launch_error("k_replay_gather_f32");
+    return launch_status("k_replay_gather_f32");
 }

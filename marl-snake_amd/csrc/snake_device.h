@@ -1,6 +1,7 @@
 // snake_device.h -- DeviceGuard, shared by the launchers of snake_kernels.hip
-// (snake_launch.inc), policy_kernels.hip and greedy_kernels.hip, and the byte
-// test the last two share. Include after <hip/hip_runtime.h> and snake_internal.h.
+// (snake_launch.inc) and of the policy, greedy, genome and replay kernels, and
+// the launch status the last four report. Include after <hip/hip_runtime.h> and
+// snake_internal.h.
 #pragma once
 
 namespace snake {
@@ -30,13 +31,13 @@ struct DeviceGuard {
     }
 };
 
-// 0x80 in every byte of x that equals 1 (exact per byte: no carry crosses a byte);
-// the channel == 1 tests of policy_kernels.hip and greedy_kernels.hip
-__device__ __forceinline__ uint32_t bytes_eq1(uint32_t x)
+// After a kernel launch: SNAKE_OK, or SNAKE_E_LAUNCH with "<kernel> launch failed: ..."
+inline int launch_status(const char *kernel)
 {
-    const uint32_t y = x ^ 0x01010101u;
-    const uint32_t t = (y & 0x7f7f7f7fu) + 0x7f7f7f7fu;
-    return ~(t | y | 0x7f7f7f7fu);
+    const hipError_t err = hipGetLastError();
+    if (err == hipSuccess) return SNAKE_OK;
+    set_error("%s launch failed: %s", kernel, hipGetErrorString(err));
+    return SNAKE_E_LAUNCH;
 }
 
 }  // namespace snake

@@ -25,16 +25,12 @@ import ctypes
 
 import numpy as np
 
-from ._native import PolicyCfg, check, lib
-from .policy import DIR_UNKNOWN, SafeActions
+from ._device import get_torch as _torch, ptr, skip_mask, stream_ptr
+from ._native import check
+from .policy import SafeActions, _ObsPolicy
 
 
-def _torch():
-    import torch
-    return torch
-
-
-class GreedyActions:
+class GreedyActions(_ObsPolicy):
     """GreedyEnemy.get_action for (N, S) snakes at once, each on its own
     observation: head for the nearest fruit by a move that does not die, ties
     broken by 32 random bits per snake.
@@ -49,17 +45,9 @@ class GreedyActions:
     starts every episode with unknown directions."""
 
     def __init__(self, obs_shape, generator=None, forget_on_reset=True, device=None, lib_path=None):
-        if len(obs_shape) != 4:
-            raise ValueError('obs_shape must be (S, h, w, 8) (got %r)' % (tuple(obs_shape),))
-        S, h, w, c = (int(v) for v in obs_shape)
-        self._L = L = lib(lib_path)
-        self.cfg = PolicyCfg(h, w, c, S, 1)     # (fill_limit: validated, not used)
-        check(L.snake_policy_plan(ctypes.byref(self.cfg)), L)      # ValueError before any device work
-        self.obs_shape = (S, h, w, c)
+        super().__init__(obs_shape, 1, device, lib_path)    # (fill_limit: validated, not used)
         self.generator = generator
         self.forget_on_reset = bool(forget_on_reset)
-        self.device = _torch().device(device) if device is not None else None   # None: the first obs's
-        self.dirs = None        # (N, S, 2) int8 (dy, dx), kept across calls when none are passed
 
     def __call__(self, obs, skip=None, dirs=None, rnd=None, slots=None):
         """obs: contiguous uint8 (N, S, h, w, 8); skip: (N, S) bool/uint8 or None
@@ -71,49 +59,27 @@ class GreedyActions:
         (N, S), ready for SnakeVecEnv.step."""
         torch = _torch()
         S = self.obs_shape[0]
-        if obs.dtype != torch.uint8 or not obs.is_contiguous():
-            raise TypeError('GreedyActions takes the observations as a contiguous uint8 tensor')
-        if obs.dim() != 5 or tuple(obs.shape[1:]) != self.obs_shape:
-            raise ValueError('obs shape %s is not (N,) + %s' % (tuple(obs.shape), self.obs_shape))
-        dev = obs.device
-        if dev.type != 'cuda':
-            raise ValueError('GreedyActions needs the observations on the GPU (got %s); there is no CPU fallback' % dev)
-        if self.device is None or (self.device.type == 'cuda' and self.device.index is None):
-            self.device = dev
-        if dev != self.device:
-            raise ValueError('obs is on %s, this GreedyActions on %s' % (dev, self.device))
-        N = obs.shape[0]
+        dev, N = self._batch(obs)
         if rnd is not None and (rnd.dtype != torch.int32 or tuple(rnd.shape) != (N, S) or not rnd.is_contiguous()
                                 or rnd.device != dev):
             raise TypeError('rnd must be a contiguous int32 (N, S) tensor on %s' % dev)
-        if dirs is not None and (dirs.dtype != torch.int8 or tuple(dirs.shape) != (N, S, 2)
-                                 or not dirs.is_contiguous() or dirs.device != dev):
-            raise TypeError('dirs must be a contiguous int8 (N, S, 2) tensor on %s' % dev)
-        if skip is not None:
-            skip = torch.as_tensor(skip, device=dev).reshape(N, S).to(torch.uint8).contiguous()
+        self._check_dirs(dirs, N, dev)
+        skip = skip_mask(skip, N, S, dev)
         if rnd is None:
             rnd = torch.randint(-2 ** 31, 2 ** 31, (N, S), dtype=torch.int32, device=dev, generator=self.generator)
-        if dirs is None:
-            if self.dirs is None or self.dirs.shape[0] != N:
-                self.dirs = torch.full((N, S, 2), DIR_UNKNOWN, dtype=torch.int8, device=dev)
-            dirs = self.dirs
+        dirs = self._dirs(dirs, N, dev)
         actions = torch.empty((N, S), dtype=torch.int8, device=dev)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        P = ctypes.c_void_p
         with torch.cuda.device(dev):
-            check(self._L.snake_greedy_actions(ctypes.byref(self.cfg), P(obs.data_ptr()), P(rnd.data_ptr()),
-                                               P(skip.data_ptr()) if skip is not None else None,
-                                               P(dirs.data_ptr()), P(actions.data_ptr()), N, stream), self._L)
+            check(self._L.snake_greedy_actions(ctypes.byref(self.cfg), ptr(obs), ptr(rnd), ptr(skip), ptr(dirs),
+                                               ptr(actions), N, stream_ptr(dev)), self._L)
         self._keep = (obs, rnd, skip)
         return actions
 
     def forget(self, mask):
         """Directions of the envs where mask (N,) is True become unknown (an
         episode ended); nothing with forget_on_reset=False."""
-        if self.forget_on_reset and self.dirs is not None:
-            torch = _torch()
-            m = torch.as_tensor(mask, device=self.dirs.device).to(torch.bool).reshape(-1, 1, 1)
-            self.dirs.masked_fill_(m, DIR_UNKNOWN)
+        if self.forget_on_reset:
+            super().forget(mask)
 
 
 class _OnSlots:

@@ -18,6 +18,7 @@ import ctypes
 
 import numpy as np
 
+from ._device import get_torch as _torch, bind_device, ptr, skip_mask, stream_ptr
 from ._native import GenomeCfg, GenomeLayout, GenomeProg, GenomeTile, check, lib
 
 RELU, SIGMOID, TANH = 0, 1, 2       # SNAKE_GENOME_RELU / _SIGMOID / _TANH
@@ -25,11 +26,6 @@ _ACT = {'relu_activation': RELU, 'relu': RELU, 'sigmoid_activation': SIGMOID, 's
         'tanh_activation': TANH, 'tanh': TANH}
 _AGG = ('sum_aggregation', 'sum')
 _FIELDS = ('node_off', 'node_act', 'node_bias', 'node_resp', 'link_off', 'link_src', 'link_w', 'out_slot')
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def _name(f):
@@ -210,12 +206,7 @@ class GenomeHeads:
             raise ValueError('features shape %s is neither (%d, %d) nor (%d, %d, %d)'
                              % (tuple(features.shape), N * S, I, N, S, I))
         dev = features.device
-        if dev.type != 'cuda':
-            raise ValueError('GenomeHeads needs the features on the GPU (got %s); there is no CPU fallback' % dev)
-        if self.device is None or (self.device.type == 'cuda' and self.device.index is None):
-            self.device = dev
-        if dev != self.device:
-            raise ValueError('features are on %s, this GenomeHeads on %s' % (dev, self.device))
+        bind_device(self, dev, 'features', 'features are')
         features = features.contiguous()
         if self._dev_prog is None:
             self._upload(dev)
@@ -224,18 +215,13 @@ class GenomeHeads:
             scratch = torch.empty(int(lay.scratch), dtype=torch.uint8, device=dev) if lay.scratch else None
             self._plans[S] = (lay, torch.from_numpy(tiles).to(dev), torch.from_numpy(rows).to(dev), scratch)
         lay, tiles, rows, scratch = self._plans[S]
-        if skip is not None:
-            skip = torch.as_tensor(skip, device=dev).reshape(N, S).to(torch.uint8).contiguous()
+        skip = skip_mask(skip, N, S, dev)
         actions = torch.empty((N, S), dtype=torch.int8, device=dev)
         outputs = torch.empty((N, S, A), dtype=torch.float64, device=dev) if return_outputs else None
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        P = ctypes.c_void_p
         with torch.cuda.device(dev):
             check(self._L.snake_genome_actions(
-                ctypes.byref(self.cfg), ctypes.byref(self._dev_prog), P(tiles.data_ptr()), P(rows.data_ptr()),
-                tiles.shape[0], P(features.data_ptr()), P(skip.data_ptr()) if skip is not None else None,
-                P(actions.data_ptr()), P(outputs.data_ptr()) if outputs is not None else None,
-                P(scratch.data_ptr()) if scratch is not None else None, N * S, stream), self._L)
+                ctypes.byref(self.cfg), ctypes.byref(self._dev_prog), ptr(tiles), ptr(rows), tiles.shape[0],
+                ptr(features), ptr(skip), ptr(actions), ptr(outputs), ptr(scratch), N * S, stream_ptr(dev)), self._L)
         self._keep = (features, skip)
         return (actions, outputs) if return_outputs else actions
 

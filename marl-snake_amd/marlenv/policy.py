@@ -12,24 +12,17 @@ DQN_Evaluator.evaluate.
 """
 import ctypes
 
+from ._device import get_torch as _torch, bind_device, ptr, skip_mask, stream_ptr
 from ._native import PolicyCfg, check, lib
 
 DIR_UNKNOWN = -128      # SNAKE_DIR_UNKNOWN: both bytes of a direction not known yet
 
 
-def _torch():
-    import torch
-    return torch
+class _ObsPolicy:
+    """What SafeActions and GreedyActions (arena.py) share: a rule on the (N, S,
+    h, w, 8) observations with one direction per snake, kept across calls."""
 
-
-class SafeActions:
-    """get_action for (N, S) snakes at once.
-
-    obs_shape: (S, h, w, 8), a SnakeVecEnv's obs_shape (frame_stack 1, h and w
-    at most 64, at most 16 snakes; anything else raises ValueError).
-    fill_limit: the flood fill's cap (the reference's 60)."""
-
-    def __init__(self, obs_shape, fill_limit=60, device=None, lib_path=None):
+    def __init__(self, obs_shape, fill_limit, device, lib_path):
         if len(obs_shape) != 4:
             raise ValueError('obs_shape must be (S, h, w, 8) (got %r)' % (tuple(obs_shape),))
         S, h, w, c = (int(v) for v in obs_shape)
@@ -40,6 +33,51 @@ class SafeActions:
         self.device = _torch().device(device) if device is not None else None   # None: the first obs's
         self.dirs = None        # (N, S, 2) int8 (dy, dx), kept across calls when none are passed
 
+    def _batch(self, obs):
+        """(device, N) of an observation batch; binds this object to its device."""
+        torch = _torch()
+        name = type(self).__name__
+        if obs.dtype != torch.uint8 or not obs.is_contiguous():
+            raise TypeError('%s takes the observations as a contiguous uint8 tensor' % name)
+        if obs.dim() != 5 or tuple(obs.shape[1:]) != self.obs_shape:
+            raise ValueError('obs shape %s is not (N,) + %s' % (tuple(obs.shape), self.obs_shape))
+        bind_device(self, obs.device, 'observations', 'obs is')
+        return obs.device, obs.shape[0]
+
+    def _check_dirs(self, dirs, N, dev):
+        torch = _torch()
+        if dirs is not None and (dirs.dtype != torch.int8 or tuple(dirs.shape) != (N, self.obs_shape[0], 2)
+                                 or not dirs.is_contiguous() or dirs.device != dev):
+            raise TypeError('dirs must be a contiguous int8 (N, S, 2) tensor on %s' % dev)
+
+    def _dirs(self, dirs, N, dev):
+        """The caller's dirs (after _check_dirs), or this object's own, all unknown when N changes."""
+        if dirs is not None:
+            return dirs
+        if self.dirs is None or self.dirs.shape[0] != N:
+            torch = _torch()
+            self.dirs = torch.full((N, self.obs_shape[0], 2), DIR_UNKNOWN, dtype=torch.int8, device=dev)
+        return self.dirs
+
+    def forget(self, mask):
+        """Directions of the envs where mask (N,) is True become unknown (an
+        episode ended: the reference starts each one with current_directions = None)."""
+        if self.dirs is not None:
+            torch = _torch()
+            m = torch.as_tensor(mask, device=self.dirs.device).to(torch.bool).reshape(-1, 1, 1)
+            self.dirs.masked_fill_(m, DIR_UNKNOWN)
+
+
+class SafeActions(_ObsPolicy):
+    """get_action for (N, S) snakes at once.
+
+    obs_shape: (S, h, w, 8), a SnakeVecEnv's obs_shape (frame_stack 1, h and w
+    at most 64, at most 16 snakes; anything else raises ValueError).
+    fill_limit: the flood fill's cap (the reference's 60)."""
+
+    def __init__(self, obs_shape, fill_limit=60, device=None, lib_path=None):
+        super().__init__(obs_shape, fill_limit, device, lib_path)
+
     def __call__(self, obs, q, skip=None, dirs=None):
         """obs: contiguous uint8 (N, S, h, w, 8); q: float32 (N, S, 3) or (N*S, 3);
         skip: (N, S) bool/uint8 or None -- snakes that get action 0 and keep
@@ -49,49 +87,21 @@ class SafeActions:
         SnakeVecEnv.step."""
         torch = _torch()
         S = self.obs_shape[0]
-        if obs.dtype != torch.uint8 or not obs.is_contiguous():
-            raise TypeError('SafeActions takes the observations as a contiguous uint8 tensor')
-        if obs.dim() != 5 or tuple(obs.shape[1:]) != self.obs_shape:
-            raise ValueError('obs shape %s is not (N,) + %s' % (tuple(obs.shape), self.obs_shape))
-        dev = obs.device
-        if dev.type != 'cuda':
-            raise ValueError('SafeActions needs the observations on the GPU (got %s); there is no CPU fallback' % dev)
-        if self.device is None or (self.device.type == 'cuda' and self.device.index is None):
-            self.device = dev
-        if dev != self.device:
-            raise ValueError('obs is on %s, this SafeActions on %s' % (dev, self.device))
-        N = obs.shape[0]
+        dev, N = self._batch(obs)
         if q.dtype != torch.float32:
             raise TypeError('SafeActions takes the Q-values as float32 (got %s)' % q.dtype)
         if tuple(q.shape) not in ((N, S, 3), (N * S, 3)):
             raise ValueError('q shape %s is neither (%d, %d, 3) nor (%d, 3)' % (tuple(q.shape), N, S, N * S))
         q = q.to(dev).contiguous()
-        if skip is not None:
-            skip = torch.as_tensor(skip, device=dev).reshape(N, S).to(torch.uint8).contiguous()
-        if dirs is None:
-            if self.dirs is None or self.dirs.shape[0] != N:
-                self.dirs = torch.full((N, S, 2), DIR_UNKNOWN, dtype=torch.int8, device=dev)
-            dirs = self.dirs
-        elif (dirs.dtype != torch.int8 or tuple(dirs.shape) != (N, S, 2) or not dirs.is_contiguous()
-              or dirs.device != dev):
-            raise TypeError('dirs must be a contiguous int8 (N, S, 2) tensor on %s' % dev)
+        skip = skip_mask(skip, N, S, dev)
+        self._check_dirs(dirs, N, dev)
+        dirs = self._dirs(dirs, N, dev)
         actions = torch.empty((N, S), dtype=torch.int8, device=dev)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        P = ctypes.c_void_p
         with torch.cuda.device(dev):
-            check(self._L.snake_safe_actions(ctypes.byref(self.cfg), P(obs.data_ptr()), P(q.data_ptr()),
-                                             P(skip.data_ptr()) if skip is not None else None,
-                                             P(dirs.data_ptr()), P(actions.data_ptr()), N, stream), self._L)
+            check(self._L.snake_safe_actions(ctypes.byref(self.cfg), ptr(obs), ptr(q), ptr(skip), ptr(dirs),
+                                             ptr(actions), N, stream_ptr(dev)), self._L)
         self._keep = (obs, q, skip)
         return actions
-
-    def forget(self, mask):
-        """Directions of the envs where mask (N,) is True become unknown (an
-        episode ended: the reference starts each one with current_directions = None)."""
-        if self.dirs is not None:
-            torch = _torch()
-            m = torch.as_tensor(mask, device=self.dirs.device).to(torch.bool).reshape(-1, 1, 1)
-            self.dirs.masked_fill_(m, DIR_UNKNOWN)
 
 
 def evaluate(env, qnet, steps, policy=None):

@@ -15,14 +15,10 @@ that is neither 0 nor 1 comes back as 1.
 """
 import ctypes
 
+from ._device import get_torch as _torch, stream_ptr
 from ._native import ReplayCfg, ReplayLayout, ReplayRings, check, lib
 
 FORMATS = {'uint8': 0, 'float32': 1}
-
-
-def _torch():
-    import torch
-    return torch
 
 
 class ReplayBuffer:
@@ -137,7 +133,7 @@ class ReplayBuffer:
             lay = ReplayLayout()
             check(self._L.snake_replay_plan(ctypes.byref(self.cfg), N, ctypes.byref(lay)), self._L)
             scratch = self._scratch[N] = torch.empty(int(lay.scratch), dtype=torch.uint8, device=dev)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = stream_ptr(dev)
         P = ctypes.c_void_p
         with torch.cuda.device(dev):
             check(self._L.snake_replay_push(
@@ -204,7 +200,7 @@ class ReplayBuffer:
         action = torch.empty(B, dtype=torch.int64, device=dev)
         reward = torch.empty(B, dtype=torch.float32, device=dev)
         done = torch.empty(B, dtype=torch.float32, device=dev)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = stream_ptr(dev)
         P = ctypes.c_void_p
         with torch.cuda.device(dev):
             check(self._L.snake_replay_gather(

@@ -32,6 +32,8 @@ sys.path.insert(0, os.path.join(ROOT, 'marl-snake_amd'))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+from launch_timer import per_launch_us  # noqa: E402
+
 I, A, S, G = 128, 3, 4, 100
 BATCHES = {'generation_100x4': 100, 'envs_4096x4': 4096}
 
@@ -63,26 +65,6 @@ def random_population(rs):
             seen.append(node)
         nets.append(Net(evals))
     return nets
-
-
-def per_launch_us(fn, inputs, launches, warmup):
-    """Median and mean device microseconds of fn(input) over `launches` launches walking round `inputs`."""
-    for i in range(warmup):
-        fn(inputs[i % len(inputs)])
-    torch.cuda.synchronize()
-    filler = torch.empty(1 << 28, dtype=torch.float32, device='cuda')
-    for _ in range(60):
-        filler.add_(1.0)
-    evs = []
-    for i in range(launches):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn(inputs[i % len(inputs)])
-        e1.record()
-        evs.append((e0, e1))
-    torch.cuda.synchronize()
-    us = sorted(a.elapsed_time(b) * 1e3 for a, b in evs)
-    return us[len(us) // 2], sum(us) / len(us)
 
 
 def random_dqn(precision, side):

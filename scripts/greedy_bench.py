@@ -38,40 +38,14 @@ sys.path.insert(0, os.path.join(ROOT, 'marl-snake_amd'))
 
 import torch  # noqa: E402
 
+from launch_timer import per_launch_us  # noqa: E402
+
 HBM_PEAK = 8.0e12
 L3_BYTES = 256 << 20
 GEOMETRIES = {
     'cfg2': dict(num_envs=4096, num_snakes=4, height=20, width=20, snake_length=5, vision_range=None),
     'cfg3': dict(num_envs=65536, num_snakes=4, height=20, width=20, snake_length=3, vision_range=5),
 }
-_filler = []
-
-
-def per_launch_us(fn, before, inputs, launches, warmup):
-    """Median and mean device microseconds of fn(input) over `launches` launches
-    walking round `inputs`; before(input) runs outside the timed span."""
-    for i in range(warmup):
-        before(inputs[i % len(inputs)])
-        fn(inputs[i % len(inputs)])
-    torch.cuda.synchronize()
-    # ~30 ms of other work first: the host enqueues every timed launch while the
-    # GPU is busy, so no span between two events waits for the host
-    if not _filler:
-        _filler.append(torch.empty(1 << 28, dtype=torch.float32, device='cuda'))
-    for _ in range(60):
-        _filler[0].add_(1.0)
-    evs = []
-    for i in range(launches):
-        x = inputs[i % len(inputs)]
-        before(x)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn(x)
-        e1.record()
-        evs.append((e0, e1))
-    torch.cuda.synchronize()
-    us = sorted(a.elapsed_time(b) * 1e3 for a, b in evs)
-    return us[len(us) // 2], sum(us) / len(us)
 
 
 def greedy_call(ga, x, rows_only):
@@ -124,7 +98,7 @@ def measure(name, launches, warmup, settle, reps):
     medians = {k[0]: [] for k in kernels}
     for _ in range(reps):
         for key, fn, before in kernels:
-            medians[key].append(per_launch_us(fn, before, inputs, launches, warmup)[0])
+            medians[key].append(per_launch_us(fn, inputs, launches, warmup, before)[0])
     out = {'num_envs': N, 'obs_shape': list(env.obs_shape), 'obs_bytes': obs_bytes, 'inputs_in_rotation': K,
            'skipped_snakes_frac': float(torch.stack([x['skip'].float().mean() for x in inputs]).mean()),
            'unknown_dirs_frac': float(torch.stack([(x['dirs_in'][..., 0] == -128).float().mean()

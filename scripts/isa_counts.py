@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Static instruction counts per kernel of snake_kernels.hip (gfx950 assembly):
+"""Static instruction counts per kernel of snake_kernels.hip, or of the source
+file the SRC environment variable names (gfx950 assembly):
 SGPR-spill lane moves (v_writelane / v_readlane: the compiler spills SGPRs into
 VGPR lanes), scratch accesses (VGPR spills), and the total, merged with the
 resource-usage remarks. One JSON object per kernel, and one
@@ -11,6 +12,7 @@ labels, so two builds whose records agree in name and body_sha run the same
 instructions.
 
     python scripts/isa_counts.py [extra hipcc flags...] > profiles/isa_counts.jsonl
+    SRC=marl-snake_amd/csrc/policy_kernels.hip python scripts/isa_counts.py
 """
 import hashlib
 import json

@@ -28,38 +28,14 @@ sys.path.insert(0, os.path.join(ROOT, 'marl-snake_amd'))
 
 import torch  # noqa: E402
 
+from launch_timer import per_launch_us  # noqa: E402
+
 HBM_PEAK = 8.0e12
 L3_BYTES = 256 << 20
 GEOMETRIES = {
     'cfg2': dict(num_envs=4096, num_snakes=4, height=20, width=20, snake_length=5, vision_range=None),
     'cfg3': dict(num_envs=65536, num_snakes=4, height=20, width=20, snake_length=3, vision_range=5),
 }
-
-
-def per_launch_us(fn, before, inputs, launches, warmup):
-    """Median and mean device microseconds of fn(input) over `launches` launches
-    walking round `inputs`; before(input) runs outside the timed span."""
-    for i in range(warmup):
-        before(inputs[i % len(inputs)])
-        fn(inputs[i % len(inputs)])
-    torch.cuda.synchronize()
-    # ~30 ms of other work first: the host enqueues every timed launch while the
-    # GPU is busy, so no span between two events waits for the host
-    filler = torch.empty(1 << 28, dtype=torch.float32, device='cuda')
-    for _ in range(60):
-        filler.add_(1.0)
-    evs = []
-    for i in range(launches):
-        x = inputs[i % len(inputs)]
-        before(x)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn(x)
-        e1.record()
-        evs.append((e0, e1))
-    torch.cuda.synchronize()
-    us = sorted(a.elapsed_time(b) * 1e3 for a, b in evs)
-    return us[len(us) // 2], sum(us) / len(us)
 
 
 def measure(name, launches, warmup, settle):
@@ -91,9 +67,8 @@ def measure(name, launches, warmup, settle):
         x['dirs'].copy_(x['dirs_in'])
 
     k_med, k_mean = per_launch_us(lambda x: sa(x['obs'], x['q'], skip=x['skip'], dirs=x['dirs']),
-                                  restore, inputs, launches, warmup)
-    r_med, r_mean = per_launch_us(lambda x: x['obs'].view(torch.int64).sum(), lambda x: None,
-                                  inputs, launches, warmup)
+                                  inputs, launches, warmup, restore)
+    r_med, r_mean = per_launch_us(lambda x: x['obs'].view(torch.int64).sum(), inputs, launches, warmup)
     return {'num_envs': N, 'obs_shape': list(env.obs_shape), 'obs_bytes': obs_bytes, 'inputs_in_rotation': K,
             'skipped_snakes_frac': float(torch.stack([x['skip'].float().mean() for x in inputs]).mean()),
             'kernel_us_median': k_med, 'kernel_us_mean': k_mean,

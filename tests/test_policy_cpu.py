@@ -76,6 +76,32 @@ def test_plan_rejects(native, args, msg):
         native.check(rc)
 
 
+def test_call_rejects_bad_arguments_on_the_host(native):
+    """Bad arguments return before any device work, so this runs without a GPU."""
+    L = native.lib()
+    buf = (ctypes.c_uint8 * 64)()
+    P = ctypes.c_void_p
+    a = ctypes.addressof(buf)
+    a16 = (a + 15) & ~15
+    ok = native.PolicyCfg(2, 2, 8, 1, 60)
+    for cfg, obs, q, dirs, act, n, rc, msg in [
+        (native.PolicyCfg(2, 2, 16, 1, 60), a16, a, a, a, 1, -1, 'obs_c'),
+        (native.PolicyCfg(65, 2, 8, 1, 60), a16, a, a, a, 1, -1, 'obs_h'),
+        (native.PolicyCfg(2, 2, 8, 17, 60), a16, a, a, a, 1, -1, 'num_snakes'),
+        (native.PolicyCfg(2, 2, 8, 1, 0), a16, a, a, a, 1, -1, 'fill_limit'),
+        (ok, None, a, a, a, 1, -2, 'NULL'), (ok, a16, None, a, a, 1, -2, 'NULL'),
+        (ok, a16, a, None, a, 1, -2, 'NULL'), (ok, a16, a, a, None, 1, -2, 'NULL'),
+        (ok, a16 + 8, a, a, a, 1, -2, 'aligned'), (ok, a16, a, a, a, -1, -2, 'num_envs'),
+        (ok, a16, a, a, a, (1 << 26) + 1, -2, 'num_envs'),
+    ]:
+        got = L.snake_safe_actions(ctypes.byref(cfg), P(obs) if obs else None, P(q) if q else None, None,
+                                   P(dirs) if dirs else None, P(act) if act else None, n, None)
+        assert got == rc, (msg, got)
+        assert msg in L.snake_last_error().decode()
+        assert 'snake_safe_actions' in L.snake_last_error().decode() or rc == -1
+    assert L.snake_safe_actions(ctypes.byref(ok), P(a16), P(a), None, P(a), P(a), 0, None) == 0   # no envs: no launch
+
+
 def test_safe_actions_rejects_a_shape_before_any_device_work(native):
     """No GPU here: the constructor raises from the host-side plan check."""
     from marlenv import SafeActions
