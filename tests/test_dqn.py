@@ -8,7 +8,13 @@ against a float64 CPU restatement (no reduced-precision conv/matmul paths).
 Tolerance (bf16 mode): the matrix products take bf16 inputs (weights and activations are
 rounded to bf16 between layers, 8 significant bits) with fp32 accumulation, so
 outputs agree with the fp32 reference to |err| <= 2e-2 * max|ref| + 1e-3 (a
-bf16-emulating reference agrees to <= 2e-3 * max|ref|, which pins the layouts)."""
+bf16-emulating reference agrees to <= 2e-3 * max|ref|, which pins the layouts).
+
+These are the tests on real weights and real observations. Layout, border, tail
+and stale-state errors too small for these bounds are held by
+tests/test_dqn_exact.py: integer probe networks (tests/dqn_probe.py, validated
+by tests/test_dqn_probe_cpu.py) on which both precisions must equal the float64
+reference, over every kernel variant and LDS plan."""
 import pytest
 
 torch = pytest.importorskip('torch')
