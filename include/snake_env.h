@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SNAKE_ABI_VERSION 19
+#define SNAKE_ABI_VERSION 20
 
 #define SNAKE_OK           0
 #define SNAKE_E_CONFIG    -1   /* invalid snake_cfg (message says which field) */
@@ -154,6 +154,36 @@ typedef struct {        /* device output buffers of one step/reset */
  * here gives up after 2^16 permutations -- sets env word 5 (and err = 2 for an
  * auto-reset) -- which the bound keeps below ~2e-6 per reset. */
 int snake_plan(const snake_cfg *cfg, int64_t num_envs, snake_layout *out);
+
+/* Which kernel variants snake_step takes for (cfg, num_envs): the launch plan's
+ * path choices, so that a test can assert the path it means to cover. Host
+ * only: needs no device and launches nothing. The per-step observation encode
+ * is described; a reset (snake_reset, and an auto-reset inside the step)
+ * always writes its observation with the direct encode. Without the all-done
+ * auto-reset (cfg->autoreset 0 or 2) the step encodes in k_encode, one env per
+ * wave, staged rows or direct only. */
+typedef struct {
+    int32_t encode;         /* per-step encode: 0 direct (one wave, no staging: more than 8 KB of
+                               observation per snake), 1 staged rows (groups of whole snakes through
+                               an LDS buffer of at most 8 KB), 2 table (one wave per 4 envs, k_post),
+                               3 lean (four-wave workgroups, k_post_lean), 4 lean + table */
+    int32_t enc_group;      /* staged rows: snakes per staged group (< num_snakes: several groups,
+                               the last one possibly partial); 0 with the direct encode; what
+                               k_encode would use where the step takes the table or lean encode */
+    int32_t units;          /* 8-byte observation units per env: S * h * w * frame_stack (odd:
+                               8-byte stores instead of 16-byte ones) */
+    int32_t enc_per_wave;   /* envs per encode wave (lean: per workgroup) */
+    int32_t enc_wpb;        /* table encode: independent encode waves per workgroup */
+    int32_t desc_in_lds;    /* table encode: the unit descriptors are read from LDS (else registers) */
+    int32_t fused;          /* the one-launch step (k_step) is eligible (snake_debug_set "fused") */
+    int32_t background;     /* spawn-ahead attempts run in the background kernel (k_spawn) */
+    int32_t link;           /* the reset workers' permutation record: 0 global link tables,
+                               1 u16 draw record in LDS, 2 u32 link table in LDS */
+    int32_t logic_lanes;    /* k_logic: lanes per env (4, 8 or 16) */
+    int32_t logic_wpb;      /* k_logic: waves per workgroup (4 or 1) */
+} snake_paths;
+
+int snake_plan_paths(const snake_cfg *cfg, int64_t num_envs, snake_paths *out);
 
 /* Host-side spawn-pose table = dfs_sweep_empty(make_grid(H, W), L) in reference
  * order (grid_util.py:73-115), as int16 cell indices r*W+c, n_cand x L. Static per

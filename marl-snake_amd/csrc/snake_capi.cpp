@@ -734,6 +734,36 @@ int snake_plan(const snake_cfg *cfg, int64_t num_envs, snake_layout *out)
     return build_kcfg(cfg, num_envs, out->n_cand, &k);
 }
 
+int snake_plan_paths(const snake_cfg *cfg, int64_t num_envs, snake_paths *out)
+{
+    if (!out) { set_error("out is NULL"); return SNAKE_E_ARG; }
+    g_err[0] = 0;
+    snake_layout lay;
+    int rc = layout_of(cfg, num_envs, &lay);
+    if (rc) return rc;
+    KCfg k;
+    if ((rc = build_kcfg(cfg, num_envs, lay.n_cand, &k))) return rc;
+    memset(out, 0, sizeof *out);
+    // the all-done auto-reset step encodes in k_post / k_post_lean (TBL, NPF < 0,
+    // else encode_obs); the other modes in k_encode, which is encode_obs only
+    const bool post = k.autoreset == 1;
+    const int obs_path = k.enc_group > 0 ? 1 : 0;
+    out->encode = !post ? obs_path : (k.lean ? (k.tbl ? 4 : 3) : (k.tbl ? 2 : obs_path));
+    out->enc_group = k.enc_group;
+    out->units = k.units;
+    out->enc_per_wave = post ? k.enc_per_wave : 1;
+    out->enc_wpb = post ? k.enc_wpb : 1;
+    // (build_kcfg's carve of tbl_desc)
+    out->desc_in_lds = post && k.tbl && (k.lean || k.units / 2 > 4 * kWave) ? 1 : 0;
+    out->fused = k.fused;
+    out->background = k.bg;
+    // k_post_lean's auto-reset workers keep no record in LDS whatever fits (snake_launch.inc launch_post)
+    out->link = k.lean && k.autoreset == 1 ? 0 : (k.link32 ? 2 : (k.link_in_lds ? 1 : 0));
+    out->logic_lanes = k.logic_ms;
+    out->logic_wpb = k.logic_wpb;
+    return SNAKE_OK;
+}
+
 int64_t snake_build_candidates(const snake_cfg *cfg, int16_t *host_out, int64_t capacity)
 {
     int rc = check_cfg(cfg);

@@ -10,10 +10,10 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libsnake_amd.so')
 
-SNAKE_ABI_VERSION = 19
+SNAKE_ABI_VERSION = 20
 
 # Symbols include/snake_env.h declares (checked by tests/test_capi.py).
-EXPORTS = ('snake_plan', 'snake_build_candidates', 'snake_seed', 'snake_reset', 'snake_step',
+EXPORTS = ('snake_plan', 'snake_plan_paths', 'snake_build_candidates', 'snake_seed', 'snake_reset', 'snake_step',
            'snake_sync', 'snake_release', 'snake_render_rgb', 'snake_timing_enable', 'snake_timing_read', 'snake_debug_set', 'snake_last_error', 'snake_abi_version',
            'snake_dqn_plan', 'snake_dqn_rows', 'snake_dqn_forward', 'snake_dqn32_scratch', 'snake_dqn32_forward',
            'snake_policy_plan', 'snake_safe_actions', 'snake_greedy_actions',
@@ -41,6 +41,15 @@ class SnakeLayout(ctypes.Structure):
         'ep_done', 'rank', 'ep_stats', 'err', 'n_cand')] + [
         ('obs_h', ctypes.c_int32), ('obs_w', ctypes.c_int32), ('obs_c', ctypes.c_int32),
         ('grid_stride', ctypes.c_int32), ('ring_cap', ctypes.c_int32)]
+
+
+class SnakePaths(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        'encode', 'enc_group', 'units', 'enc_per_wave', 'enc_wpb', 'desc_in_lds', 'fused', 'background',
+        'link', 'logic_lanes', 'logic_wpb')]
+
+
+ENCODE_PATHS = ('direct', 'rows', 'table', 'lean', 'lean_table')   # SnakePaths.encode
 
 
 class SnakeState(ctypes.Structure):
@@ -140,6 +149,7 @@ def lib(path=None):
     L.snake_abi_version.restype = ctypes.c_int
     L.snake_last_error.restype = ctypes.c_char_p
     L.snake_plan.argtypes = [ctypes.POINTER(SnakeCfg), I64, ctypes.POINTER(SnakeLayout)]
+    L.snake_plan_paths.argtypes = [ctypes.POINTER(SnakeCfg), I64, ctypes.POINTER(SnakePaths)]
     L.snake_build_candidates.restype = I64
     L.snake_build_candidates.argtypes = [ctypes.POINTER(SnakeCfg), P, I64]
     L.snake_seed.argtypes = [ctypes.POINTER(SnakeCfg), ctypes.POINTER(SnakeState), I64,
@@ -180,6 +190,16 @@ def lib(path=None):
         raise NativeError('libsnake_amd.so ABI version mismatch; rebuild it')
     _libs[path] = L
     return L
+
+
+def plan_paths(num_envs, L=None, **kw):
+    """snake_plan_paths (include/snake_env.h) as a dict: the kernel variants
+    snake_step takes for a SnakeVecEnv(num_envs, **kw). Host only, no device."""
+    from .config import build_cfg
+    L = L or lib()
+    out = SnakePaths()
+    check(L.snake_plan_paths(ctypes.byref(build_cfg(**kw)[0]), int(num_envs), ctypes.byref(out)), L)
+    return {n: int(getattr(out, n)) for n, _ in SnakePaths._fields_}
 
 
 def timing_enable(on, L=None):

@@ -19,6 +19,7 @@ tests/golden/:
                       (grid_util.py:14-20, 73-115).
 * traj_<name>.npz  -- seeded trajectories: per-step rewards, dones, grids,
                       obs digests, episode info at all-done, reset grids.
+                      traj_rect_*: boards with height != width.
 * crafted.json     -- hand-built states injected into env.grid/env.snakes,
                       then stepped: head-on, tail entry, fruit-eater tail rule,
                       double decrement, self-kill, win, truncation, dead crop,
@@ -97,6 +98,13 @@ def make_candidates():
     for H, W, L in [(40, 40, 3), (20, 20, 5), (12, 12, 4), (20, 20, 3), (10, 10, 3)]:
         a = cand_array(H, W, L)
         meta.append((H, W, L, a.shape[0], digest(a)))
+    # rectangular boards (H != W): row and column of the sweep are not interchangeable
+    for H, W, L in [(6, 9, 2), (9, 6, 2), (7, 12, 3)]:
+        out[f'full_{H}x{W}_L{L}'] = cand_array(H, W, L)
+    for H, W, L in [(12, 20, 3), (20, 12, 3), (5, 255, 3), (255, 5, 3), (24, 40, 3), (30, 72, 3)]:
+        a = cand_array(H, W, L)
+        meta.append((H, W, L, a.shape[0], digest(a)))
+        print(f'candidates {H}x{W} L{L}: {a.shape[0]}')
     out['digest_meta'] = np.array(meta, dtype=np.uint64)
     np.savez_compressed(os.path.join(OUT, 'candidates.npz'), **out)
 
@@ -247,6 +255,35 @@ def make_trajs():
              eps=0.0, vision_range=4, full_obs_every=300)
 
 
+def make_rect_trajs():
+    # boards with height != width (vision crop, full map, both orientations, the
+    # 255 limit of either side): every one records at least 3 resets
+    run_traj('rect_12x20_vr5_s4', 250, 30, height=12, width=20, num_snakes=4, vision_range=5,
+             full_obs_every=50)
+    run_traj('rect_20x12_s4', 250, 31, height=20, width=12, num_snakes=4, full_obs_every=50)
+    run_traj('rect_14x9_s3', 200, 32, height=14, width=9, num_snakes=3, full_obs_every=50)
+    run_traj('rect_9x14_vr3_fs2_s3', 200, 33, height=9, width=14, num_snakes=3, vision_range=3,
+             frame_stack=2, full_obs_every=50)
+    run_traj('rect_7x22_human_vr2_s2', 200, 34, height=7, width=22, num_snakes=2, vision_range=2,
+             observer='human', full_obs_every=50)
+    run_traj('rect_coop_10x16_vr4_s3', 200, 35, coop=True, height=10, width=16, num_snakes=3,
+             vision_range=4, full_obs_every=50)
+    run_traj('rect_24x8_greedy_s2', 600, 36, height=24, width=8, num_snakes=2, snake_length=2,
+             policy='greedy', eps=0.05, full_obs_every=150)
+    # an 11x11 crop on a board 8 rows high
+    run_traj('rect_8x36_vr5_s4', 250, 37, height=8, width=36, num_snakes=4, vision_range=5,
+             full_obs_every=50)
+    run_traj('rect_5x255_vr4_s2', 200, 38, height=5, width=255, num_snakes=2, vision_range=4,
+             full_obs_every=50)
+    run_traj('rect_255x5_vr3_fs2_s2', 200, 39, height=255, width=5, num_snakes=2, vision_range=3,
+             frame_stack=2, full_obs_every=50)
+    run_traj('rect_23x25_s2', 200, 40, height=23, width=25, num_snakes=2, full_obs_every=50)
+    run_traj('rect_13x15_fs3_s3', 200, 41, height=13, width=15, num_snakes=3, frame_stack=3,
+             full_obs_every=50)
+    run_traj('rect_24x40_vr5_fs4_s8', 250, 42, height=24, width=40, num_snakes=8, vision_range=5,
+             frame_stack=4, max_episode_steps=60, full_obs_every=50)
+
+
 # ---------------------------------------------------------- crafted scenarios
 def inject(env, H, W, fruits, snakes, alive_snakes=None, episode_length=0):
     """Build grid + Snake objects exactly as reset() paints them (snake_env.py:131-159)."""
@@ -382,6 +419,23 @@ def make_crafted():
     cases.append(crafted_case('two_eaters', 7, 7, [(1, 3), (5, 3)],
                               [([(1, 2), (1, 1)], True), ([(5, 4), (5, 5)], True)],
                               [[0, 0], [1, 1], [0, 0]], seed=23, reward_dict=R))
+    # 14. 6x12: snake 0 runs right from column 8 and dies only at column 11, snake 1
+    #     runs down from row 3 and dies at row 5 (a transposed board kills them at
+    #     other steps)
+    cases.append(crafted_case('rect_wide_walls', 6, 12, [(4, 8)],
+                              [([(1, 8), (1, 7)], True), ([(3, 3), (2, 3)], True)],
+                              [[0, 0], [0, 0], [0, 0]], seed=24, reward_dict=R))
+    #     ... and its mirror image on 12x6
+    cases.append(crafted_case('rect_tall_walls', 12, 6, [(8, 4)],
+                              [([(8, 1), (7, 1)], True), ([(3, 3), (3, 2)], True)],
+                              [[0, 0], [0, 0], [0, 0]], seed=24, reward_dict=R))
+    # 15. 6x12, 7x7 crop, two frames: a head at (4, 10), its crop over the right and
+    #     bottom walls and off the board on both axes, then up the last column to
+    #     (1, 10) (off the top); snake 1's crop hangs off the top left corner
+    cases.append(crafted_case('rect_crop_corner', 6, 12, [(3, 8), (2, 2)],
+                              [([(4, 10), (4, 9), (4, 8)], True), ([(1, 3), (1, 2)], True)],
+                              [[1, 0], [0, 0], [0, 0]], seed=25, vision_range=3, frame_stack=2,
+                              reward_dict=R))
     with open(os.path.join(OUT, 'crafted.json'), 'w') as fp:
         json.dump(cases, fp, indent=0)
     for c in cases:
@@ -400,3 +454,5 @@ if __name__ == '__main__':
         make_trajs()
     if 'traj' in which or 'coop' in which:
         make_coop_trajs()
+    if 'traj' in which or 'rect' in which:
+        make_rect_trajs()

@@ -6,6 +6,7 @@ workgroup's envs, stepped against the CPU oracle and compared at every step
 import numpy as np
 import pytest
 
+import plan_cases
 from parity_util import compare_step, oracle_batch
 
 torch = pytest.importorskip('torch')
@@ -33,6 +34,11 @@ GEOMETRIES = {
     # more than four chunks per lane (descriptors in LDS) / three frame dwords per lane
     'fs2_12_vr3': (dict(height=12, width=12, vision_range=3, frame_stack=2), 4),
     'b24_vr3': (dict(height=24, width=24, vision_range=3), 4),
+    # height != width (paths in plan_cases.PLAN under 'geom_' + name): table
+    # encode in both orientations, a staged encode in groups of 3 of 4 snakes,
+    # the direct encode
+    **{k: plan_cases.PLAN['geom_' + k][:2] for k in ('rect_12x20_s4', 'rect_20x12_vr5_s4', 'rect_14x22_s4',
+                                                     'rect_23x25_s2')},
 }
 
 
@@ -78,6 +84,8 @@ def test_odd_batch_sizes(oracle, N, path):
 @pytest.mark.parametrize('geom', sorted(GEOMETRIES))
 def test_geometries(oracle, geom, path):
     kw, S = GEOMETRIES[geom]
+    if 'geom_' + geom in plan_cases.PLAN:
+        plan_cases.check('geom_' + geom, dict(kw, **PATHS[path]), S, 37, **PATHS[path])
     _run(oracle, dict(kw, **PATHS[path]), S, 37, 40, 5000 + len(geom) + 7 * S, f'{geom} {path}')
 
 

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import golden_io as G
+import plan_cases
 from parity_util import compare_step, oracle_batch
 
 torch = pytest.importorskip('torch')
@@ -164,6 +165,23 @@ BATCH_CASES = {
     'fused_24_vr3': (dict(height=24, width=24, vision_range=3, spawn_background=-1), 4, 64, 100),
 }
 
+# Boards with height != width, one per encode path and orientation, and the
+# direct encode (rectangular or not): shapes and planned paths in plan_cases.PLAN
+# (asserted before stepping); name -> steps. Each must see at least N episode
+# ends, so that reset, spawn table and repaint run on its board (the large
+# boards carry max_episode_steps=60 for that).
+RECT_BATCH_STEPS = {
+    'rect_wide_12x20': 150, 'rect_tall_20x12_vr5': 150, 'rect_flat_8x36_vr5': 150,
+    'fused_rect_12x20': 150, 'fused_rect_20x12_vr5': 150, 'fused_rect_8x36_vr5': 150,
+    'rect_lean_24x40_fs4': 200, 'rect_lean_40x24_vr8_fs4': 200, 'rect_lean_32x48_fs2_full': 200,
+    'rect_rows_14x9': 150, 'rect_rows_9x14_vr3_fs2': 150, 'rect_rows_9x7_l2': 150,
+    'rect_rows_7x22_human_vr2': 150, 'rect_rows_14x22_groups': 150, 'rect_rows_22x14_groups': 150,
+    'direct_23x25': 150, 'direct_25x23_s3': 150, 'direct_13x15_fs3': 150, 'direct_40x40_s8_full': 200,
+    'rect_thin_5x255_vr4': 120, 'rect_thin_255x5_vr3_fs2': 120,
+    'rect_big_30x72_vr4': 200, 'rect_big_72x30_vr4': 200, 'rect_big_64x150_l2': 200,
+}
+BATCH_CASES.update({k: plan_cases.PLAN[k][:3] + (T,) for k, T in RECT_BATCH_STEPS.items()})
+
 
 @pytest.fixture
 def fused_on():
@@ -181,6 +199,8 @@ def test_batch_matches_oracle(oracle, case, request):
     if case.startswith('fused_'):
         request.getfixturevalue('fused_on')
     kw, S, N, T = BATCH_CASES[case]
+    if case in plan_cases.PLAN:   # the path the case is for is the path planned
+        plan_cases.check(case, kw, S, N)
     seed = 1000 + 17 * len(case)
     v = SnakeVecEnv(N, num_snakes=S, seed=seed, **kw)
     obs0 = _np(v.reset())
@@ -189,11 +209,16 @@ def test_batch_matches_oracle(oracle, case, request):
     np.testing.assert_array_equal(obs0, robs)
     rs = np.random.RandomState(seed)
     n_act = 5 if kw.get('observer') == 'human' else 3
+    ends = 0
     for t in range(T):
         a = rs.randint(0, n_act, size=(N, S))
         obs, rew, done, info = v.step(torch.from_numpy(a))
-        compare_step(refs, range(N), a, _np(obs), _np(rew), _np(done), _np(info),
+        info = _np(info)
+        ends += int(info['episode_done'].sum())
+        compare_step(refs, range(N), a, _np(obs), _np(rew), _np(done), info,
                      grids=_np(v.grids()), where=f'{case} step {t}')
+    if case in RECT_BATCH_STEPS:
+        assert ends >= N, f'{case}: {ends} episode ends in {N} envs x {T} steps'
 
 
 @pytest.mark.parametrize('N,kw,fused', [
@@ -280,6 +305,10 @@ FULL_SIZE_CASES = {
     # NPF = 1) and of 65 to 128 (NPF = 2)
     'odd14_16384': (16384, 4, 100, dict(height=14, width=14, vision_range=3)),
     'odd34_16384': (16384, 4, 120, dict(height=34, width=34, vision_range=3)),
+    # height != width: the table encode with 4-lane k_logic, and the staged
+    # encode at two envs per encode wave
+    'rect_12x20_vr5_16384': (16384, 4, 100, dict(height=12, width=20, snake_length=3, vision_range=5)),
+    'rect_14x22_vr3_16384': (16384, 4, 100, dict(height=14, width=22, vision_range=3)),
 }
 
 
@@ -292,6 +321,8 @@ def test_full_size_sampled_parity(oracle, case):
     from marlenv import SnakeVecEnv
     N, S, T, kw = FULL_SIZE_CASES[case][:4]
     off = FULL_SIZE_CASES[case][4] if len(FULL_SIZE_CASES[case]) > 4 else 0
+    if case in plan_cases.PLAN:
+        plan_cases.check(case, kw, S, N)
     vr = kw['vision_range']
     v = SnakeVecEnv(N, num_snakes=S, seed=0, env_offset=off, **kw)
     obs = v.reset()
@@ -462,6 +493,11 @@ def test_make_snake_surface():
     assert env.action_space.n == 3
     obs = env.reset()
     assert obs.shape == (4, 11, 11, 8) and obs.dtype == np.uint8
+    rect, _, _, _ = make_snake(num_envs=1, num_snakes=3, height=9, width=14)   # full map: (S, H, W, 8)
+    assert rect.observation_space.shape == (3, 9, 14, 8)
+    o = rect.reset()
+    assert o.shape == (3, 9, 14, 8) and o.dtype == np.uint8
+    assert rect.step([0, 1, 2])[0].shape == (3, 9, 14, 8)
     acts = [env.action_space.sample() for _ in range(4)]
     obs2, rews, dones, info = env.step(acts)
     assert len(rews) == 4 and all(isinstance(r, float) for r in rews)
@@ -479,7 +515,8 @@ def test_make_snake_surface():
 
 @pytest.mark.parametrize('S,kw', [(4, dict(height=20, width=20, vision_range=5)),
                                   (16, dict(height=24, width=24, snake_length=2, vision_range=3)),
-                                  (3, dict(height=9, width=7, snake_length=2))])
+                                  (3, dict(height=9, width=7, snake_length=2)),
+                                  (2, dict(height=7, width=22))])
 def test_render_rgb_matches_oracle(S, kw):
     """k_render (snake_render_rgb) == rgb_from_grid (grid_util.py:164-175) of the
     current grids, checked by the oracle's cell-by-cell restatement, along a
@@ -541,7 +578,8 @@ def test_info_zero_where_episode_continues():
                                   (dict(height=44, width=44, vision_range=4, spawn_ahead=4), 4),
                                   (dict(height=40, width=40, vision_range=5, frame_stack=4,
                                         spawn_background=-1), 8),
-                                  (dict(height=20, width=20, vision_range=5, spawn_background=1), 4)])
+                                  (dict(height=20, width=20, vision_range=5, spawn_background=1), 4),
+                                  (dict(height=12, width=20, vision_range=5), 4)])
 def test_snapshot_restore_roundtrip(kw, S):
     """state_dict() mid-episode -> K steps -> load_state_dict() -> the same K steps
     reproduce bit-identically, in the same env and in a fresh one (and from a
@@ -629,7 +667,8 @@ def test_vec_env_on_non_current_device():
 
 
 @pytest.mark.parametrize('S,kw', [(4, dict(height=20, width=20, vision_range=5)),
-                                  (2, dict(height=12, width=12, snake_length=4))])
+                                  (2, dict(height=12, width=12, snake_length=4)),
+                                  (3, dict(height=9, width=14, vision_range=3))])
 def test_autoreset_every_step_matches_oracle(oracle, S, kw):
     """autoreset='every_step' (gym 0.23.1's worker behind make_snake,
     wrappers.py:212): the step's rewards/dones/info, then a reset of every env,

@@ -75,8 +75,8 @@ def plan(native, h, w, c, S, capacity, N=0):
 
 
 def test_abi_version(native):
-    assert native.SNAKE_ABI_VERSION == 19
-    assert native.lib().snake_abi_version() == 19
+    assert native.SNAKE_ABI_VERSION == 20
+    assert native.lib().snake_abi_version() == 20
 
 
 def test_plan_sizes(native):
