@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build alternative libsnake_amd.so variants into marl-snake_amd/build/var/ for
 # in-process A/B timing (scripts/ab_probe.py). Usage: build_variants.sh tag:flags ...
-#   tag:flags   -> current sources compiled with extra flags (e.g. lb4:-DSNAKE_STEP_MIN_WAVES=4)
+#   tag:flags   -> current sources compiled with extra flags (e.g. stamps:-DSNAKE_STAMPS)
 #   tag@commit  -> the sources of a git commit
 set -eu
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

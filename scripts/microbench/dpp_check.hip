@@ -1,44 +1,14 @@
-// Checks the DPP lane-group exchanges of snake_kernels.hip (gsel, gscan) against
-// their definitions on random values: prints "dpp ok" or the first mismatches.
-// hipcc --offload-arch=gfx950 -O3 -std=c++17 -I. dpp_check.hip -o dpp_check
+// Checks the DPP lane-group exchanges of the step kernels (gsel, gscan of
+// marl-snake_amd/csrc/step_lanes.h, the code that ships) against their
+// definitions on random values: prints "dpp ok" or the first mismatches.
+// hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../../marl-snake_amd/csrc dpp_check.hip -o dpp_check
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include <utility>
-#include <type_traits>
-#include <stdint.h>
 
-__device__ __forceinline__ int dpp_pin(int x) { __asm__ volatile("" : "+v"(x)); return x; }
-template <int G, int J>
-__device__ __forceinline__ int gsel(int v)
-{
-    if constexpr (G == 4) {
-        return dpp_pin(__builtin_amdgcn_mov_dpp(v, J * 0x55, 0xf, 0xf, false));
-    } else if constexpr (G == 16) {
-        return dpp_pin(__builtin_amdgcn_mov_dpp(v, 0x150 + J, 0xf, 0xf, false));
-    } else {
-        const int t = dpp_pin(__builtin_amdgcn_mov_dpp(v, (J & 3) * 0x55, 0xf, 0xf, false));
-        if constexpr (J < 4) return dpp_pin(__builtin_amdgcn_update_dpp(t, t, 0x114, 0xf, 0xa, false));
-        else return dpp_pin(__builtin_amdgcn_update_dpp(t, t, 0x104, 0xf, 0x5, false));
-    }
-}
-template <int G>
-__device__ __forceinline__ int gscan(int v, int k)
-{
-    int x = dpp_pin(__builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false));
-    v += k >= 1 ? x : 0;
-    x = dpp_pin(__builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false));
-    v += k >= 2 ? x : 0;
-    if constexpr (G >= 8) { x = dpp_pin(__builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false)); v += k >= 4 ? x : 0; }
-    if constexpr (G >= 16) { x = dpp_pin(__builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false)); v += k >= 8 ? x : 0; }
-    return v;
-}
-// the same exchanges under a divergent branch in the caller (must still be right
-// for the lanes that take it, reading lanes that do not)
-template <typename F, int... I>
-__device__ __forceinline__ void unroll_seq(F &&f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, typename F>
-__device__ __forceinline__ void unroll(F &&f) { unroll_seq(f, std::make_integer_sequence<int, N>{}); }
+#include "step_lanes.h"
+
+using namespace snake;
 
 template <int G>
 __global__ void k(const int *in, int *out)

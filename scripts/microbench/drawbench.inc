@@ -1,9 +1,11 @@
 // drawbench.inc -- diagnostic only, compiled into libsnake_amd.so by a build
 // with -DSNAKE_DRAWBENCH (scripts/build_variants.sh dbench:-DSNAKE_DRAWBENCH;
 // read by scripts/drawbench.py and scripts/attemptbench.py). Included at the end
-// of marl-snake_amd/csrc/snake_kernels.hip, after namespace snake: the
-// cooperative four-wave permutation draws of round 5 (identical records, 2.1-2.5x
-// slower than one wave: not kept, DESIGN.md) and the isolated benchmarks.
+// of marl-snake_amd/csrc/snake_kernels.hip, after namespace snake, and using
+// the device functions of its step_*.h headers (step_mt.h, step_perm.h,
+// step_reset.h): the cooperative four-wave permutation draws of round 5
+// (identical records, 2.1-2.5x slower than one wave: not kept, DESIGN.md) and
+// the isolated benchmarks.
 namespace snake {
 // ------------------------------------------------ cooperative permutation draws
 // permutation(n)'s draws (the records of mt_perm_draws) on the kCoopW waves of
