@@ -417,6 +417,64 @@ int snake_greedy_actions(const snake_policy_cfg *cfg, const uint8_t *obs, const 
                          const uint8_t *skip, int8_t *dirs, int8_t *actions,
                          int64_t num_envs, void *stream);
 
+/* ---- Graph observation: the ray-cast features of the reference's third env
+ * id, SnakeGraph-v1 (graph_snake_env.py:47-103 GraphSnakeEnv._process_obs), for
+ * every snake at once: 5 rays x obs_c values per snake, a pure function of the
+ * observation tensor snake_step / snake_reset wrote and of the snake records
+ * (st->snake, int32 [N][S][4]: word 0 = head row | head column << 8 | ..., word
+ * 1 = direction (bits 0-1: 0 UP, 1 RIGHT, 2 DOWN, 3 LEFT) | alive << 8 | ...;
+ * the other words are not read). Nothing that outlives snake_step writes
+ * st->snake (the background spawn kernel writes st->spawn and env word 4 only),
+ * so the call needs no snake_sync, only stream order after the step.
+ *
+ * A dead snake's 5 x obs_c values are zero. For a live snake, with n =
+ * vision_range steps from the origin (vr, vr), the window's centre -- or, with
+ * vision_range 0 (full-map observations), n = 5 steps from the snake's own head
+ * cell -- and (dr, dc) the unit step of its direction ((-1,0), (0,1), (1,0),
+ * (0,-1) for 0..3), ray k steps by
+ *     0: F = (dr, dc)   1: L = (-dc, dr)   2: R = (dc, -dr)   3: F + L   4: F + R
+ * and is, per channel, a float64 sum that starts at 0.0: for i = 0 .. n-1 in
+ * order the cell origin + (i+1) * step is read; every channel whose byte is 1
+ * adds w[i]; after that, if the cell's channel 0 is 1 (a wall in the oldest
+ * frame of the stack) the ray ends -- the wall cell is counted. A cell outside
+ * the observation ends the ray unread (the reference never gets there for a
+ * live snake; the kernel reads nothing outside whatever the records hold).
+ * w[i] = 1 / (i+1) for rays 0-2 and 1 / ((i+1) * sqrt(2.0)) for rays 3-4, as
+ * the reference's arithmetic gives them: with a window its observation is
+ * float64 and w[i] the float64 quotient; its full-map observation is float32
+ * and w[i] = (double)(1.0f / (float)(i+1)), (double)(1.0f / (float)((i+1) *
+ * sqrt(2.0))).
+ *
+ * source 0 ("own"): snake s reads observation s. source 1 ("reference"): the
+ * reference indexes the observations with a counter of the LIVE snakes, so
+ * live snake s reads observation k = the number of live snakes below s (with
+ * the origin, for full maps, still s's own head): what GraphSnakeEnv returns,
+ * live rows compacted, is this mode's live rows in index order. */
+typedef struct {
+    int32_t obs_h, obs_w;       /* observation height and width, 1..255; 2 * vision_range + 1 with a window */
+    int32_t obs_c;              /* observation channels: 8 * frame_stack, 8..128 */
+    int32_t num_snakes;         /* S, 1..16 */
+    int32_t vision_range;       /* 0 == None (full-map observations), else 1..127 */
+    int32_t source;             /* 0 own, 1 reference */
+    int32_t out_f32;            /* 0: float64 out; 1: float out, the float64 result rounded once */
+} snake_graph_cfg;
+
+/* Validates cfg (host only, no device needed; SNAKE_E_CONFIG names the field). */
+int snake_graph_plan(const snake_graph_cfg *cfg);
+
+/* The weights of `steps` ray steps (1..127) as the kernel gets them: host_out
+ * double [2][steps], row 0 rays 0-2, row 1 the diagonals; float32_quotient != 0
+ * is the full-map arithmetic. Host only. */
+int snake_graph_weights(int32_t steps, int32_t float32_quotient, double *host_out);
+
+/* obs: uint8 [N][S][h][w][obs_c], 8-byte aligned; snake_records: int32
+ * [N][S][4], 16-byte aligned; out: double (or float) [N][S][5][obs_c], 16-byte
+ * aligned; num_envs in [0, 2^26] with num_envs * S * 5 * obs_c / 2 <= 2^31 (0:
+ * no launch). One launch (k_graph_obs) on `stream`, on the stream's device;
+ * reads obs and snake_records, writes every value of out. */
+int snake_graph_obs(const snake_graph_cfg *cfg, const uint8_t *obs, const int32_t *snake_records,
+                    void *out, int64_t num_envs, void *stream);
+
 /* ---- Replay buffer: the reference trainer's deque of transitions
  * (train_dqn.py:89-100 ReplayBuffer, filled at :290-298, sampled at :228-240)
  * as rings in device memory, filled straight from one env step's tensors.

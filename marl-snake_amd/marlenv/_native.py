@@ -18,7 +18,8 @@ EXPORTS = ('snake_plan', 'snake_plan_paths', 'snake_build_candidates', 'snake_se
            'snake_dqn_plan', 'snake_dqn_rows', 'snake_dqn_forward', 'snake_dqn32_scratch', 'snake_dqn32_forward',
            'snake_policy_plan', 'snake_safe_actions', 'snake_greedy_actions',
            'snake_replay_plan', 'snake_replay_push', 'snake_replay_gather',
-           'snake_genome_plan', 'snake_genome_check', 'snake_genome_tiles', 'snake_genome_actions')
+           'snake_genome_plan', 'snake_genome_check', 'snake_genome_tiles', 'snake_genome_actions',
+           'snake_graph_plan', 'snake_graph_weights', 'snake_graph_obs')
 
 
 class SnakeCfg(ctypes.Structure):
@@ -123,6 +124,11 @@ class GenomeLayout(ctypes.Structure):
                 ('lds_nodes', ctypes.c_int32), ('lds_bytes', ctypes.c_int32)]
 
 
+class GraphCfg(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('obs_h', 'obs_w', 'obs_c', 'num_snakes', 'vision_range', 'source',
+                                              'out_f32')]
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -182,6 +188,9 @@ def lib(path=None):
     L.snake_genome_tiles.restype = I64
     L.snake_genome_actions.argtypes = [ctypes.POINTER(GenomeCfg), ctypes.POINTER(GenomeProg), P, P, I64, P, P, P, P,
                                        P, I64, P]
+    L.snake_graph_plan.argtypes = [ctypes.POINTER(GraphCfg)]
+    L.snake_graph_weights.argtypes = [ctypes.c_int32, ctypes.c_int32, P]
+    L.snake_graph_obs.argtypes = [ctypes.POINTER(GraphCfg), P, P, P, I64, P]
     L.snake_timing_enable.argtypes = [ctypes.c_int]
     L.snake_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_longlong]
     L.snake_timing_read.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_double),

@@ -1,12 +1,14 @@
 """Env ids (reference marlenv/marlenv/envs/__init__.py:3-16)."""
 from .coop_snake_env import CoopSnakeEnv
+from .graph_snake_env import GraphSnakeEnv  # noqa: F401
 from .snake_env import SnakeEnv
 
 REGISTRY = {
     'Snake-v1': SnakeEnv,
     'SnakeCoop-v1': CoopSnakeEnv,
 }
-# 'SnakeGraph-v1' (graph_snake_env.py: ray-cast feature obs) is out of scope.
+# 'SnakeGraph-v1' (graph_snake_env.py: ray-cast feature obs) is not served under
+# its id yet: wrappers.make_graph_snake / GraphSnakeEnv / GraphVecEnv provide it.
 UNSUPPORTED = {'SnakeGraph-v1'}
 
 

@@ -19,6 +19,7 @@ every env is reset after every step (rewards/dones/info of the step, the reset o
 """
 import ctypes
 import sys
+from weakref import ref as _weakref
 
 import numpy as np
 
@@ -195,6 +196,7 @@ class SnakeVecEnv:
         self.observation_space = spaces.Box(0, 255, (N,) + self.obs_shape, np.uint8)
         self.action_space = spaces.Box(0, self.action_n - 1, (N, S), np.int64)
         self._reset_done = False
+        self._obs_ref = None
         self._palette = None
         self._plan_slab()
         # the step's ctypes call with its constant arguments prebuilt
@@ -298,7 +300,8 @@ class SnakeVecEnv:
                                       ctypes.byref(so), self._stream()))
         self._keep = m
         self._reset_done = True
-        return self._view(slab, 'obs')
+        self._obs_ref = _weakref(slab[0])
+        return slab[0]
 
     def step(self, actions):
         """SnakeEnv.step (snake_env.py:301-414) for every env.
@@ -329,6 +332,7 @@ class SnakeVecEnv:
         if rc < 0:
             check(rc, self._L)
         self._keep = a
+        self._obs_ref = _weakref(slab[0])
         info = _StepInfo(self, slab, stream)
         if self.strict and bool(info['error'].any()):
             err = info['error']
@@ -338,6 +342,12 @@ class SnakeVecEnv:
             raise RuntimeError(f'auto-reset gave up placing disjoint snakes in envs '
                                f'{(err == 2).nonzero().flatten().tolist()[:8]}')
         return slab[0], slab[2], slab[3], info
+
+    def latest_obs(self):
+        """The observation tensor the last reset() or step() returned, while the
+        caller still holds it (the env keeps no reference of its own: a dropped
+        buffer is the one the next step gets back); else None."""
+        return self._obs_ref() if self._obs_ref is not None else None
 
     def render_rgb(self):
         """rgb_from_grid of every env's current grid (grid_util.py:164-175), on the

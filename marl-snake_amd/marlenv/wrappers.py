@@ -10,11 +10,15 @@ SingleAgent does inside each reference worker).
 AsyncVectorMultiEnv (the process pool) is replaced by SnakeVecEnv. RenderGUI is
 kept as a pass-through wrapper so callers that import or wrap with it run
 unchanged; drawing an OpenCV window / video is out of scope (render() raises).
+make_graph_snake is make_snake for the reference's third env id, 'SnakeGraph-v1'
+(ray-cast graph features in place of the grid observation); make_snake itself
+still refuses that id.
 """
 import numpy as np
 
 from . import spaces
-from .envs import REGISTRY, UNSUPPORTED
+from .envs import REGISTRY, UNSUPPORTED, GraphSnakeEnv
+from .graph import GraphVecEnv
 from .vec_env import SnakeVecEnv
 
 
@@ -127,6 +131,29 @@ def make_snake(num_envs=1, num_snakes=4, env_id='Snake-v1', **kwargs):
         env = env_wrapper(REGISTRY[env_id](num_snakes=num_snakes, **kwargs))
     properties = {
         'action_info': {'action_n': action_n},
+        'num_envs': num_envs,
+        'num_snakes': num_snakes,
+    }
+    return env, None, None, properties
+
+
+def make_graph_snake(num_envs=1, num_snakes=4, **kwargs):
+    """make_snake(env_id='SnakeGraph-v1') of the reference (wrappers.py:203-223 over
+    graph_snake_env.py). num_envs == 1: the single-env GraphSnakeEnv in the
+    reference's wrappers, returning what the reference returns (live rows only,
+    uint8). num_envs > 1: a GraphVecEnv -- float features (N, S, 5, C) on the
+    GPU, zero rows for dead snakes; source= and dtype= go to it."""
+    if kwargs.get('observer', 'snake') != 'snake':
+        raise ValueError("This is not yet implemented for 'human' observers.")
+    if num_envs > 1:
+        env = GraphVecEnv(num_envs, num_snakes=num_snakes, **kwargs)
+        if num_snakes == 1:
+            env = SingleAgentVec(env)
+    else:
+        env_wrapper = SingleMultiAgent if num_snakes > 1 else SingleAgent
+        env = env_wrapper(GraphSnakeEnv(num_snakes=num_snakes, **kwargs))
+    properties = {
+        'action_info': {'action_n': 3},
         'num_envs': num_envs,
         'num_snakes': num_snakes,
     }
