@@ -34,6 +34,7 @@ _W12x20 = dict(height=12, width=20)
 _T20x12 = dict(height=20, width=12, vision_range=5)
 _F8x36 = dict(height=8, width=36, vision_range=5)
 _FUSED = dict(encode=TABLE, fused=1, background=0, link=2, enc_per_wave=4)
+_GROW12 = dict(height=12, width=12, snake_length=3, num_fruits=10, vision_range=3)
 
 PLAN = {
     # ---- existing cases of test_gpu_parity whose comments claim a path
@@ -112,6 +113,15 @@ PLAN = {
     'geom_rect_20x12_vr5_s4': (_T20x12, 4, 37, dict(encode=TABLE, desc_in_lds=0)),
     'geom_rect_14x22_s4': (dict(height=14, width=22), 4, 37, dict(encode=ROWS, enc_group=3)),
     'geom_rect_23x25_s2': (dict(height=23, width=25), 2, 37, dict(encode=DIRECT)),
+    # ---- long snakes under the growing policy (grow_policy.CASES): the k_logic
+    # instantiations whose body-ring code they are for
+    # 32 envs: at least 8 lanes, and a small batch runs the background kernel
+    'grow_12_s4': (_GROW12, 4, 32, dict(logic_lanes=8, background=1)),
+    'fused_grow_12_s4': (dict(_GROW12, **INSTEP), 4, 32, _FUSED),
+    # past 8192 envs S <= 4 runs 4 lanes per env, 16 envs per wave
+    'grow_12_s4_16384': (_GROW12, 4, 16384, dict(logic_lanes=4)),
+    'grow_24_s16': (dict(height=24, width=24, snake_length=2, num_fruits=40, vision_range=3), 16, 16,
+                    dict(logic_lanes=16)),
 }
 
 

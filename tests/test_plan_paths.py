@@ -82,10 +82,13 @@ def test_plan_paths_errors(native):
 
 def test_rows_are_the_shapes_the_gpu_tests_run():
     """A row of the table and the GPU case of the same name are one shape."""
+    import grow_policy
     import test_encode_blocks as eb
     import test_gpu_parity as gp
     for name, (kw, S, N, _) in P.PLAN.items():
-        if name in gp.BATCH_CASES:
+        if name in grow_policy.CASES:
+            assert grow_policy.CASES[name][:3] == (kw, S, N), name
+        elif name in gp.BATCH_CASES:
             assert gp.BATCH_CASES[name][:3] == (kw, S, N), name
         elif name in gp.FULL_SIZE_CASES:
             assert gp.FULL_SIZE_CASES[name][:2] + (gp.FULL_SIZE_CASES[name][3],) == (N, S, kw), name
