@@ -291,7 +291,8 @@ int snake_debug_set(const char *name, long long value);
 typedef struct {
     int32_t height, width, channels, num_actions;
     int32_t conv_waves;     /* waves per observation in the conv kernel: 1, 2, 4; 0 = default (4,
-                             * or 2 when the row-tile count is odd; SNAKE_DQN_WAVES overrides 0) */
+                             * or 2 when the row-tile count is odd; SNAKE_DQN_WAVES overrides 0);
+                             * the map path (snake_dqn_map_*): 8, 16; 0 = default (16) */
 } snake_dqn_cfg;
 
 typedef struct {        /* sizes for snake_dqn_forward (element counts) */
@@ -331,6 +332,21 @@ int64_t snake_dqn_rows(const snake_dqn_cfg *cfg, int32_t *rows, int64_t n);
 int snake_dqn_forward(const snake_dqn_cfg *cfg, const snake_dqn_net *net, const uint8_t *obs,
                       int64_t batch, uint16_t *act_scratch, float *q_out, float *feat_out,
                       void *stream);
+
+/* The map path of the bf16 forward: the same network, layouts and roundings on
+ * any h x w observation (rectangular included) with (h+2)*(w+2) <= 576, i.e. up
+ * to 22x22 (train_dqn.py's 20x20 full map: 26 row tiles, p16 = 416), c in {8,
+ * 16, 24, 32}, A <= 4. cfg->conv_waves: waves per workgroup of its convolution
+ * kernel, 8 or 16; 0 = default (16). One workgroup runs one observation at a
+ * time and loops over the row tiles, so h and w are runtime values. Same
+ * structs and argument lists as the three functions above, whose window path
+ * (3x3 .. 11x11) stays the faster one where it applies. What the plan rejects
+ * is SNAKE_E_CONFIG; larger maps take fp32 mode below. */
+int snake_dqn_map_plan(const snake_dqn_cfg *cfg, snake_dqn_layout *out);
+int64_t snake_dqn_map_rows(const snake_dqn_cfg *cfg, int32_t *rows, int64_t n);
+int snake_dqn_map_forward(const snake_dqn_cfg *cfg, const snake_dqn_net *net, const uint8_t *obs,
+                          int64_t batch, uint16_t *act_scratch, float *q_out, float *feat_out,
+                          void *stream);
 
 /* fp32 mode of the DQN consumer (dqn32_kernels.hip): the same network in fp32
  * arithmetic (fp32 matrix cores: exact fp32 products, fp32 sums) on any observation size (e.g. train_dqn.py's 20x20 full map,

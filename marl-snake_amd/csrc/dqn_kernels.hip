@@ -8,7 +8,7 @@
 //   flatten NCHW (index ch*h*w + y*w + x) -> fc1 (64hw->256) + ReLU
 //   -> fc2 (256->128) + ReLU (= forward_features) -> fc3 (128->A)
 //
-// Two kernels:
+// Three kernels:
 //   k_dqn_conv  one wave per observation (many per CU): the three convolutions
 //               as implicit GEMMs on v_mfma_f32_16x16x32_bf16, rows = the h*w
 //               positions (padded to 16), columns = output channels, K = 9 taps
@@ -23,6 +23,10 @@
 //               32-wide k step staged once in LDS for all 8 waves (double
 //               buffered); then per wave fc2 on the matrix cores (h1 from LDS)
 //               and fc3 in fp32 on the vector units.
+//   k_dqn_map_conv  the convolutions of a whole-map observation (up to 22x22, h
+//               and w runtime values) in k_dqn_conv's place: one workgroup of 8
+//               or 16 waves per observation, a loop over the row tiles; same
+//               scratch layout, same k_dqn_fc (snake_dqn_map_forward).
 // Accumulation is fp32 everywhere; inputs and weights of the matrix products
 // are bf16 (tolerance against the fp32 reference: tests/test_dqn.py).
 #include <hip/hip_runtime.h>
@@ -565,6 +569,208 @@ __global__ void __launch_bounds__(512) k_dqn_fc(const FcArgs a)
     if (wv < 4) __syncthreads();
 }
 
+// ---- k_dqn_map_conv -----------------------------------------------------
+// The map path: the three convolutions of any h x w observation whose bordered
+// image has at most kMapCells cells (22x22 positions), h and w runtime values.
+// One workgroup of NW waves (8 or 16) runs one observation at a time in a
+// persistent grid. The LDS images are k_dqn_conv's (chunk-major 16-byte cells,
+// zero border, plane size CH a runtime value); the input image always lies over
+// a2. Every write into an image goes to an interior cell, so the borders,
+// zeroed once, stay zero. The GEMM rows are dqn_row_of's assignment (the 16
+// rows of a tile in distinct banks), built on the host in O(h*w) and passed as
+// a kernel argument (tab: border index of every row, 0xffff for a padding row).
+//
+// A wave owns NTW output channel tiles of a layer and every RG-th row tile. It
+// keeps its weight fragments of the whole layer in registers (conv3: 18 k steps
+// x NTW x 4 VGPRs), loaded before the barrier that ends the layer before, and
+// loops over its row tiles with NTW accumulators: per k step one 16-byte LDS
+// read and NTW MFMAs (8 waves: NTW = 2 in conv2 and conv3, 16 waves: 1). The tap offsets are wave-uniform for 32 and 64 input
+// channels (one tap per k step or two); conv1 with 8 or 16 padded channels
+// has several taps per k step, one per lane quad.
+// conv3's output has k_dqn_conv's layout, padding rows included (they hold
+// finite values and meet zero fc1 weights).
+constexpr int kMapCells = 576;               // (h + 2) * (w + 2) at most
+constexpr int kMapRows = 576;                // GEMM rows at most: 16 * ceil(kMapCells / 16)
+constexpr int kMapMaxP = 484;                // h * w at most under kMapCells (22 x 22)
+constexpr int kMapMaxLds = 12 * kMapCells * 16 + 2 * kMapRows;
+
+struct MapArgs {
+    ConvArgs c;
+    int H, W, MT, CH;                        // CH: bytes per 8-channel plane
+    uint16_t tab[kMapRows];
+};
+
+// byte offset of the lane's A fragment of k step ks from the cell one row and
+// one column before the GEMM row's own: k = ks * 32 + 8 * quad = tap << CL | channel
+template <int CL>
+__device__ __forceinline__ int map_aoff(int ks, int quad, int bw16, int ch)
+{
+    const int k0 = ks * 32 + 8 * quad, tap = k0 >> CL, ci = k0 & ((1 << CL) - 1);
+    const int t = tap < 9 ? tap : 4;         // taps past the 9th meet zero weights
+    return (t / 3) * bw16 + (t % 3) * 16 + (ci >> 3) * ch;
+}
+
+// The weights do not change from one observation to the next, so the compiler
+// would hoist all three layers' loads out of the persistent loop and spill
+// them: an offset of zero that it cannot see through ties each load to its place.
+template <int KS, int NTW>
+__device__ __forceinline__ void map_load_w(bf16x8 (&wr)[KS][NTW], const uint16_t *__restrict__ wt, int nt0, int lane)
+{
+    int here = 0;
+    asm volatile("" : "+s"(here));
+    const uint8_t *p = reinterpret_cast<const uint8_t *>(wt) + 16 * lane + here;
+#pragma unroll
+    for (int ks = 0; ks < KS; ks++)
+#pragma unroll
+        for (int j = 0; j < NTW; j++) wr[ks][j] = *reinterpret_cast<const bf16x8 *>(p + 1024 * ((nt0 + j) * KS + ks));
+}
+
+// one row tile: acc[j] = A(tile m of the image at src) x wr[.][j]
+template <int CL, int KS, int NTW>
+__device__ __forceinline__ void map_mma(const uint8_t *lds, int src, const uint16_t *ptab, int m, int lane, int bw16,
+                                        int ch, const bf16x8 (&wr)[KS][NTW], f32x4 (&acc)[NTW])
+{
+    const int r16 = lane & 15, quad = lane >> 4;
+    const int q = ptab[m * 16 + r16];
+    // a padding row gathers around the first interior cell (finite values, results unused)
+    const int base = src + (q != 0xffff ? q * 16 - bw16 - 16 : 0);
+#pragma unroll
+    for (int j = 0; j < NTW; j++) acc[j] = (f32x4)0.0f;
+#pragma unroll
+    for (int ks = 0; ks < KS; ks++) {
+        const bf16x8 av = *reinterpret_cast<const bf16x8 *>(lds + base + map_aoff<CL>(ks, quad, bw16, ch));
+#pragma unroll
+        for (int j = 0; j < NTW; j++) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, wr[ks][j], acc[j], 0, 0, 0);
+    }
+}
+
+// bias + ReLU -> bf16 into the interior cells of the image at dst
+template <int NTW>
+__device__ __forceinline__ void map_store_lds(uint8_t *lds, int dst, const uint16_t *ptab, int m, int nt0, int lane,
+                                              int ch, const float (&bias)[NTW], const f32x4 (&acc)[NTW])
+{
+    const int r16 = lane & 15, quad = lane >> 4;
+    const uint2 pq = *reinterpret_cast<const uint2 *>(ptab + m * 16 + 4 * quad);
+    const uint32_t q[4] = {pq.x & 0xffffu, pq.x >> 16, pq.y & 0xffffu, pq.y >> 16};
+#pragma unroll
+    for (int j = 0; j < NTW; j++) {
+        const int co = (nt0 + j) * 16 + r16;
+        const int cbase = dst + (co >> 3) * ch + 2 * (co & 7);
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            if (q[r] != 0xffffu)
+                *reinterpret_cast<uint16_t *>(lds + cbase + q[r] * 16) = (uint16_t)bf16_bits(fmaxf(acc[j][r] + bias[j], 0.0f));
+        }
+    }
+}
+
+template <int CL, int NW>
+__global__ void __launch_bounds__(64 * NW) k_dqn_map_conv(const MapArgs a)
+{
+    constexpr int NT = 64 * NW, CP = 1 << CL, G8 = CP / 8;
+    constexpr int K1S = (9 * CP + 31) / 32;
+    // channel tiles per wave: both of conv1; two (8 waves) or one (16 waves) of
+    // the four of conv2 and conv3. RG: waves that share the row tiles of a layer
+    constexpr int NT1 = 2, NT3 = NW == 8 ? 2 : 1;
+    constexpr int RG1 = NW, RG3 = NW / (4 / NT3);
+    constexpr int NC = (kMapMaxP * G8 + NT - 1) / NT;
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r16 = lane & 15;
+    const int H = a.H, W = a.W, MT = a.MT, CH = a.CH, C = a.c.C;
+    const int BW = W + 2, P = H * W, bw16 = BW * 16;
+    const int OFF1 = 0, OFF2 = 4 * CH, OFFT = 12 * CH;
+    const int cs3 = wv % (4 / NT3), rg3 = wv / (4 / NT3), nt3 = cs3 * NT3;
+    uint16_t *ptab = reinterpret_cast<uint16_t *>(lds + OFFT);
+    for (int i = tid; i < 12 * CH / 16; i += NT) reinterpret_cast<u32x4 *>(lds)[i] = (u32x4)0u;
+    for (int i = tid; i < MT * 16; i += NT) ptab[i] = a.tab[i];
+    // input cells of this thread (cell c: chunk c / P, position c % P): source
+    // byte offset within the observation (-1: a padded channel chunk, zero) and
+    // LDS byte offset (-1: no cell)
+    int csrc[NC], cdst[NC];
+#pragma unroll
+    for (int i = 0; i < NC; i++) {
+        const int c = tid + NT * i;
+        const int g = c / P, p = c - g * P;
+        const int y = p / W, x = p - y * W;
+        const bool have = c < P * G8;
+        csrc[i] = have && g * 8 < C ? p * C + g * 8 : -1;
+        cdst[i] = have ? OFF2 + g * CH + ((y + 1) * BW + x + 1) * 16 : -1;
+    }
+    uint2 xin[NC];
+    auto load_obs = [&](int64_t b) {
+        const uint8_t *x = a.c.obs + b * (int64_t)(P * C);
+#pragma unroll
+        for (int i = 0; i < NC; i++) xin[i] = csrc[i] >= 0 ? *reinterpret_cast<const uint2 *>(x + csrc[i]) : make_uint2(0, 0);
+    };
+    float bias1[NT1], bias2[NT3], bias3[NT3];
+#pragma unroll
+    for (int j = 0; j < NT1; j++) bias1[j] = a.c.b1[j * 16 + r16];
+#pragma unroll
+    for (int j = 0; j < NT3; j++) {
+        bias2[j] = a.c.b2[(nt3 + j) * 16 + r16];
+        bias3[j] = a.c.b3[(nt3 + j) * 16 + r16];
+    }
+    int64_t b = blockIdx.x;
+    if (b < a.c.B) load_obs(b);
+    bf16x8 w1[K1S][NT1];
+    map_load_w<K1S, NT1>(w1, a.c.w1, 0, lane);
+    __syncthreads();
+    for (; b < a.c.B; b += gridDim.x) {
+#pragma unroll
+        for (int i = 0; i < NC; i++)
+            if (cdst[i] >= 0) *reinterpret_cast<u32x4 *>(lds + cdst[i]) = bytes_to_bf16(xin[i]);
+        if (b + gridDim.x < a.c.B) load_obs(b + gridDim.x);
+        __syncthreads();
+        bf16x8 w2[9][NT3];
+        {   // conv1: CP -> 32, a0 (over a2) -> a1
+            for (int m = wv; m < MT; m += RG1) {
+                f32x4 acc[NT1];
+                map_mma<CL, K1S, NT1>(lds, OFF2, ptab, m, lane, bw16, CH, w1, acc);
+                map_store_lds<NT1>(lds, OFF1, ptab, m, 0, lane, CH, bias1, acc);
+            }
+            map_load_w<9, NT3>(w2, a.c.w2, nt3, lane);
+        }
+        __syncthreads();
+        bf16x8 w3[18][NT3];
+        {   // conv2: 32 -> 64, a1 -> a2
+            for (int m = rg3; m < MT; m += RG3) {
+                f32x4 acc[NT3];
+                map_mma<5, 9, NT3>(lds, OFF1, ptab, m, lane, bw16, CH, w2, acc);
+                map_store_lds<NT3>(lds, OFF2, ptab, m, nt3, lane, CH, bias2, acc);
+            }
+            map_load_w<18, NT3>(w3, a.c.w3, nt3, lane);
+        }
+        __syncthreads();
+        {   // conv3: 64 -> 64, a2 -> global in MFMA fragment order (16 bytes of
+            // lane l, row tile m, channel tile pair h at ((m * 2 + h) * 64 + l) * 16:
+            // tile 2h in the low 8 bytes, 2h + 1 in the high)
+            uint8_t *dst = reinterpret_cast<uint8_t *>(a.c.act + b * (int64_t)(64 * MT * 16)) + 16 * lane;
+            for (int m = rg3; m < MT; m += RG3) {
+                f32x4 acc[NT3];
+                map_mma<6, 18, NT3>(lds, OFF2, ptab, m, lane, bw16, CH, w3, acc);
+                uint2 v[NT3];
+#pragma unroll
+                for (int j = 0; j < NT3; j++) {
+                    v[j].x = pack2(fmaxf(acc[j][0] + bias3[j], 0.0f), fmaxf(acc[j][1] + bias3[j], 0.0f));
+                    v[j].y = pack2(fmaxf(acc[j][2] + bias3[j], 0.0f), fmaxf(acc[j][3] + bias3[j], 0.0f));
+                }
+                if constexpr (NT3 == 2) {
+                    u32x4 o;
+                    o[0] = v[0].x; o[1] = v[0].y; o[2] = v[1].x; o[3] = v[1].y;
+                    *reinterpret_cast<u32x4 *>(dst + (m * 2 + cs3) * 1024) = o;
+                } else {
+                    *reinterpret_cast<uint2 *>(dst + (m * 2 + (cs3 >> 1)) * 1024 + (cs3 & 1) * 8) = v[0];
+                }
+            }
+            // unconditional: behind a condition w1 would stay live (and spill) through conv2 and conv3
+            map_load_w<K1S, NT1>(w1, a.c.w1, 0, lane);
+        }
+        __syncthreads();   // the next input image overwrites a2
+    }
+}
+
 }  // namespace dqn
 }  // namespace snake
 
@@ -694,6 +900,159 @@ extern "C" int snake_dqn_forward(const snake_dqn_cfg *cfg, const snake_dqn_net *
     hipLaunchKernelGGL(kc, dim3(gconv), dim3(64 * nw), 0, s, ca);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) { set_error("k_dqn_conv launch failed: %s", hipGetErrorString(err)); return SNAKE_E_LAUNCH; }
+    FcArgs fa;
+    fa.act = act_scratch; fa.B = batch; fa.K = (int)lay.act_per_obs; fa.A = cfg->num_actions;
+    fa.w4 = net->fc1_w; fa.b4 = net->fc1_b; fa.w5 = net->fc2_w; fa.b5 = net->fc2_b;
+    fa.w6 = net->fc3_w; fa.b6 = net->fc3_b; fa.q = q_out; fa.feat = feat_out;
+    const unsigned gfc = (unsigned)((batch + kFcObs - 1) / kFcObs);
+    hipLaunchKernelGGL(k_dqn_fc, dim3(gfc), dim3(512), 0, s, fa);
+    err = hipGetLastError();
+    if (err != hipSuccess) { set_error("k_dqn_fc launch failed: %s", hipGetErrorString(err)); return SNAKE_E_LAUNCH; }
+    return SNAKE_OK;
+}
+
+// ---- the map path's host side --------------------------------------------
+namespace {
+typedef void (*map_kernel_t)(MapArgs);
+struct MapKernel {
+    map_kernel_t k;
+    int lds, grid;      // the persistent grid at `lds` bytes of LDS per workgroup (0: not asked yet)
+    bool big_lds;       // the kernel may be launched with kMapMaxLds
+};
+MapKernel g_map[2][3] = {
+    {{k_dqn_map_conv<3, 8>, 0, 0, false}, {k_dqn_map_conv<4, 8>, 0, 0, false}, {k_dqn_map_conv<5, 8>, 0, 0, false}},
+    {{k_dqn_map_conv<3, 16>, 0, 0, false}, {k_dqn_map_conv<4, 16>, 0, 0, false}, {k_dqn_map_conv<5, 16>, 0, 0, false}},
+};
+// waves per observation in k_dqn_map_conv when snake_dqn_cfg.conv_waves is 0.
+// 16 384 observations of 20x20x8: the kernel takes 0.77 ms with 16 waves, 0.87 ms with 8.
+int map_conv_waves() { return 16; }
+
+// dqn_row_of for every position in O(h*w): row tiles, and per GEMM row the
+// border index (tab) and the position (rows); either may be null
+int map_rows(int H, int W, uint16_t *tab, int32_t *rows)
+{
+    int cnt[16] = {0}, mt = 0;
+    for (int p = 0; p < H * W; p++) mt = std::max(mt, ++cnt[dqn_bidx(p, W) & 15]);
+    for (int i = 0; i < mt * 16; i++) {
+        if (tab) tab[i] = (uint16_t)0xffffu;
+        if (rows) rows[i] = -1;
+    }
+    for (int r = 0; r < 16; r++) cnt[r] = 0;
+    for (int p = 0; p < H * W; p++) {
+        const int q = dqn_bidx(p, W), i = cnt[q & 15]++ * 16 + (q & 15);
+        if (tab) tab[i] = (uint16_t)q;
+        if (rows) rows[i] = p;
+    }
+    return mt;
+}
+}  // namespace
+
+extern "C" int snake_dqn_map_plan(const snake_dqn_cfg *cfg, snake_dqn_layout *out)
+{
+    if (!cfg || !out) { set_error("snake_dqn_map_plan: NULL argument"); return SNAKE_E_ARG; }
+    const int H = cfg->height, W = cfg->width, C = cfg->channels, A = cfg->num_actions;
+    if (H < 1 || W < 1 || (int64_t)(H + 2) * (W + 2) > kMapCells) {
+        set_error("snake_dqn_map: the bordered observation (h+2)*(w+2) must have 9 to %d cells (up to 22x22), got "
+                  "%dx%d; larger maps take fp32 mode (precision='fp32', snake_dqn32_forward)", kMapCells, H, W);
+        return SNAKE_E_CONFIG;
+    }
+    if (C < 8 || C > 32 || C % 8) {
+        set_error("snake_dqn_map: channels must be 8 * frame_stack in [8, 32] (got %d); other counts take fp32 mode "
+                  "(precision='fp32', snake_dqn32_forward)", C);
+        return SNAKE_E_CONFIG;
+    }
+    if (A < 1 || A > 4) {
+        set_error("snake_dqn_map: num_actions must be in [1, 4] (got %d); more take fp32 mode (precision='fp32', "
+                  "snake_dqn32_forward)", A);
+        return SNAKE_E_CONFIG;
+    }
+    if (cfg->conv_waves != 0 && cfg->conv_waves != 8 && cfg->conv_waves != 16) {
+        set_error("snake_dqn_map: conv_waves must be 0, 8 or 16 (got %d)", cfg->conv_waves);
+        return SNAKE_E_CONFIG;
+    }
+    int cl = 3;
+    while ((1 << cl) < C) cl++;
+    const int P16 = map_rows(H, W, nullptr, nullptr) * 16, CP = 1 << cl;
+    const int NB = (H + 2) * (W + 2);
+    out->cpad = CP;
+    out->p16 = P16;
+    out->k1 = (9 * CP + 31) / 32 * 32;
+    out->conv1_w = 32ll * out->k1;
+    out->conv2_w = 64ll * 288;
+    out->conv3_w = 64ll * 576;
+    out->fc1_w = 256ll * 64 * P16;
+    out->fc2_w = 128ll * 256;
+    out->act_per_obs = 64ll * P16;
+    out->lds_conv = (int32_t)(12 * ((NB + 15) / 16) * 256 + 2 * P16);
+    return SNAKE_OK;
+}
+
+extern "C" int64_t snake_dqn_map_rows(const snake_dqn_cfg *cfg, int32_t *rows, int64_t n)
+{
+    snake_dqn_layout lay;
+    const int rc = snake_dqn_map_plan(cfg, &lay);
+    if (rc) return rc;
+    if (rows) {
+        if (n < lay.p16) { set_error("snake_dqn_map_rows: need %d entries", lay.p16); return SNAKE_E_ARG; }
+        map_rows(cfg->height, cfg->width, nullptr, rows);
+    }
+    return lay.p16;
+}
+
+extern "C" int snake_dqn_map_forward(const snake_dqn_cfg *cfg, const snake_dqn_net *net, const uint8_t *obs,
+                                     int64_t batch, uint16_t *act_scratch, float *q_out, float *feat_out,
+                                     void *stream)
+{
+    snake_dqn_layout lay;
+    int rc = snake_dqn_map_plan(cfg, &lay);
+    if (rc) return rc;
+    if (!net || !obs || !act_scratch || !q_out || !net->conv1_w || !net->conv2_w || !net->conv3_w ||
+        !net->fc1_w || !net->fc2_w || !net->conv1_b || !net->conv2_b || !net->conv3_b || !net->fc1_b ||
+        !net->fc2_b || !net->fc3_w || !net->fc3_b) {
+        set_error("snake_dqn_map_forward: NULL buffer");
+        return SNAKE_E_ARG;
+    }
+    if (batch < 0) { set_error("snake_dqn_map_forward: batch < 0"); return SNAKE_E_ARG; }
+    if (batch == 0) return SNAKE_OK;
+    const hipStream_t s = (hipStream_t)stream;
+    MapArgs ma;
+    ma.c.obs = obs; ma.c.B = batch; ma.c.C = cfg->channels;
+    ma.c.w1 = net->conv1_w; ma.c.w2 = net->conv2_w; ma.c.w3 = net->conv3_w;
+    ma.c.b1 = net->conv1_b; ma.c.b2 = net->conv2_b; ma.c.b3 = net->conv3_b;
+    ma.c.act = act_scratch;
+    ma.H = cfg->height; ma.W = cfg->width;
+    ma.CH = (((cfg->height + 2) * (cfg->width + 2) + 15) / 16) * 256;
+    for (int i = 0; i < kMapRows; i++) ma.tab[i] = (uint16_t)0xffffu;
+    ma.MT = map_rows(cfg->height, cfg->width, ma.tab, nullptr);
+    if (ma.MT * 16 != lay.p16 || lay.lds_conv > kMapMaxLds || lay.lds_conv != 12 * ma.CH + 2 * lay.p16) {
+        set_error("snake_dqn_map_forward: plan and row table disagree");
+        return SNAKE_E_CONFIG;
+    }
+    const int nw = cfg->conv_waves ? cfg->conv_waves : map_conv_waves();
+    MapKernel &mk = g_map[nw == 16][lay.cpad == 8 ? 0 : (lay.cpad == 16 ? 1 : 2)];
+    if (!mk.big_lds) {   // more than the 64 KB a launch may ask for without it
+        if (hipFuncSetAttribute((const void *)mk.k, hipFuncAttributeMaxDynamicSharedMemorySize, kMapMaxLds) != hipSuccess) {
+            set_error("snake_dqn_map_forward: cannot raise the kernel's LDS limit to %d bytes", kMapMaxLds);
+            return SNAKE_E_LAUNCH;
+        }
+        mk.big_lds = true;
+    }
+    if (mk.lds != lay.lds_conv) {   // persistent grid: the resident workgroups of the whole device
+        int per_cu = 0, dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)mk.k, 64 * nw, lay.lds_conv) != hipSuccess ||
+            per_cu < 1 || cus < 1) {
+            set_error("snake_dqn_map_forward: occupancy query failed");
+            return SNAKE_E_LAUNCH;
+        }
+        mk.grid = per_cu * cus;
+        mk.lds = lay.lds_conv;
+    }
+    const unsigned gconv = (unsigned)std::min<int64_t>(batch, mk.grid);
+    hipLaunchKernelGGL(mk.k, dim3(gconv), dim3(64 * nw), lay.lds_conv, s, ma);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) { set_error("k_dqn_map_conv launch failed: %s", hipGetErrorString(err)); return SNAKE_E_LAUNCH; }
     FcArgs fa;
     fa.act = act_scratch; fa.B = batch; fa.K = (int)lay.act_per_obs; fa.A = cfg->num_actions;
     fa.w4 = net->fc1_w; fa.b4 = net->fc1_b; fa.w5 = net->fc2_w; fa.b5 = net->fc2_b;

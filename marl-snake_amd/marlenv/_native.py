@@ -16,6 +16,7 @@ SNAKE_ABI_VERSION = 20
 EXPORTS = ('snake_plan', 'snake_plan_paths', 'snake_build_candidates', 'snake_seed', 'snake_reset', 'snake_step',
            'snake_sync', 'snake_release', 'snake_render_rgb', 'snake_timing_enable', 'snake_timing_read', 'snake_debug_set', 'snake_last_error', 'snake_abi_version',
            'snake_dqn_plan', 'snake_dqn_rows', 'snake_dqn_forward', 'snake_dqn32_scratch', 'snake_dqn32_forward',
+           'snake_dqn_map_plan', 'snake_dqn_map_rows', 'snake_dqn_map_forward',
            'snake_policy_plan', 'snake_safe_actions', 'snake_greedy_actions',
            'snake_replay_plan', 'snake_replay_push', 'snake_replay_gather',
            'snake_genome_plan', 'snake_genome_check', 'snake_genome_tiles', 'snake_genome_actions',
@@ -171,6 +172,10 @@ def lib(path=None):
     L.snake_dqn_rows.argtypes = [ctypes.POINTER(DqnCfg), P, I64]
     L.snake_dqn_rows.restype = I64
     L.snake_dqn_forward.argtypes = [ctypes.POINTER(DqnCfg), ctypes.POINTER(DqnNet), P, I64, P, P, P, P]
+    L.snake_dqn_map_plan.argtypes = L.snake_dqn_plan.argtypes
+    L.snake_dqn_map_rows.argtypes = L.snake_dqn_rows.argtypes
+    L.snake_dqn_map_rows.restype = I64
+    L.snake_dqn_map_forward.argtypes = L.snake_dqn_forward.argtypes
     L.snake_dqn32_scratch.argtypes = [ctypes.POINTER(DqnCfg), I64]
     L.snake_dqn32_scratch.restype = I64
     L.snake_dqn32_forward.argtypes = [ctypes.POINTER(DqnCfg), ctypes.POINTER(Dqn32Net), P, I64, P, P, P, P]

@@ -110,7 +110,8 @@ class SafeDQN(_OnSlots):
     """The battle's slot 0: a DQN behind the safe-action rule, as a controller.
 
     qnet: any callable from uint8 (B, h, w, 8) observations to float32 (B, 3),
-    e.g. DQNForward(..., precision='fp32'); it runs on the observations of the
+    e.g. DQNForward(...) (bf16, any map up to 22x22) or DQNForward(...,
+    precision='fp32'); it runs on the observations of the
     controller's own slots only. With several slots the rule's claimed cells
     apply among them, in slot order, as in the evaluator; with one slot the set
     is empty, which is what BattleArena passes (train_dqn.py:925)."""

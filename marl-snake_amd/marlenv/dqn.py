@@ -8,12 +8,15 @@ the same network is the frozen feature extractor of train_ga.py:60-100):
     x = relu(fc1(x.reshape(B, -1))); x = relu(fc2(x))            # forward_features
     q = fc3(x)
 
-DQNForward runs it through snake_dqn_forward (marl-snake_amd/csrc/dqn_kernels.hip):
-implicit-GEMM convolutions and the fc layers on the bf16 matrix cores, fp32
-accumulation. The weights come from a state dict with the reference's parameter
-names (conv1.weight, ..., fc3.bias) and are packed once into the kernel layouts
-(include/snake_env.h snake_dqn_layout); packing is a layout transform done with
-torch ops, the forward pass is the HIP kernels only.
+DQNForward runs it through snake_dqn_forward or snake_dqn_map_forward
+(marl-snake_amd/csrc/dqn_kernels.hip): implicit-GEMM convolutions and the fc
+layers on the bf16 matrix cores, fp32 accumulation. The window plan holds the
+square vision windows 3x3 to 11x11, the map plan any map up to 22x22 (the
+reference's own 20x20 full map); both feed the same fc kernel. The weights
+come from a state dict with the reference's parameter names (conv1.weight, ...,
+fc3.bias) and are packed once into the kernel layouts (include/snake_env.h
+snake_dqn_layout); packing is a layout transform done with torch ops, the
+forward pass is the HIP kernels only.
 """
 import ctypes
 
@@ -23,6 +26,10 @@ from ._native import Dqn32Net, DqnCfg, DqnLayout, DqnNet, check, lib
 def _torch():
     import torch
     return torch
+
+
+# conv_waves values snake_dqn_map_plan accepts (0: the library's default, 16)
+MAP_CONV_WAVES = (0, 8, 16)
 
 
 # The reference network's parameter shapes (train_dqn.py:104-151): the kernels
@@ -49,11 +56,15 @@ class DQNForward:
     state: a state dict (or nn.Module) of the reference DQN (conv1..conv3, fc1..fc3).
     conv_waves: waves per observation in the conv kernel (0 = the library default).
     precision: 'bf16' (the fused MFMA kernels: bf16 products, fp32 accumulation;
-    square odd maps up to 11x11, 8-32 channels) or 'fp32' (dqn32_kernels.hip:
-    fp32 arithmetic on any map, e.g. train_dqn.py's 20x20 full-map Config)."""
+    8-32 channels) or 'fp32' (dqn32_kernels.hip: fp32 arithmetic on any map).
+    plan (bf16 only): 'window' (square odd maps 3x3 to 11x11, conv_waves 1, 2 or
+    4), 'map' (any h x w with (h+2)*(w+2) <= 576, e.g. train_dqn.py's 20x20
+    full-map Config; conv_waves in MAP_CONV_WAVES) or 'auto' (window where it
+    accepts the geometry, else map). The plan in use is self.plan (None in
+    fp32 mode)."""
 
     def __init__(self, state, height, width, channels, num_actions=3, device=None, lib_path=None, conv_waves=0,
-                 precision='bf16'):
+                 precision='bf16', plan='auto'):
         torch = _torch()
         if hasattr(state, 'state_dict'):
             state = state.state_dict()
@@ -62,7 +73,10 @@ class DQNForward:
         self.cfg = DqnCfg(int(height), int(width), int(channels), int(num_actions), int(conv_waves))
         if precision not in ('bf16', 'fp32'):
             raise ValueError("precision must be 'bf16' or 'fp32'")
+        if plan not in ('auto', 'window', 'map'):
+            raise ValueError("plan must be 'auto', 'window' or 'map'")
         self.precision = precision
+        self.plan = None
         self.num_actions = int(num_actions)
         self._scratch = None
         _check_shapes(state, int(channels), int(height) * int(width), int(num_actions))
@@ -70,7 +84,13 @@ class DQNForward:
             self._init_fp32(state)
             return
         lay = DqnLayout()
-        check(L.snake_dqn_plan(ctypes.byref(self.cfg), ctypes.byref(lay)), L)
+        if plan == 'auto':
+            plan = 'window' if L.snake_dqn_plan(ctypes.byref(self.cfg), ctypes.byref(lay)) == 0 else 'map'
+        self.plan = plan
+        plan_fn, rows_fn, self._forward_fn = (
+            (L.snake_dqn_plan, L.snake_dqn_rows, L.snake_dqn_forward) if plan == 'window' else
+            (L.snake_dqn_map_plan, L.snake_dqn_map_rows, L.snake_dqn_map_forward))
+        check(plan_fn(ctypes.byref(self.cfg), ctypes.byref(lay)), L)
         self.layout = lay
         H, W, C, A = int(height), int(width), int(channels), int(num_actions)
         P, P16, CP, K1 = H * W, lay.p16, lay.cpad, lay.k1
@@ -103,7 +123,7 @@ class DQNForward:
         # k in conv3's fragment order (snake_env.h snake_dqn_layout.fc1_w) -> the
         # reference's NCHW flatten index channel * h*w + position
         rows = (ctypes.c_int32 * P16)()
-        n = L.snake_dqn_rows(ctypes.byref(self.cfg), ctypes.cast(rows, ctypes.c_void_p), P16)
+        n = rows_fn(ctypes.byref(self.cfg), ctypes.cast(rows, ctypes.c_void_p), P16)
         if n != P16:
             check(int(n) if n < 0 else -1, L)
         rowpos = torch.tensor(list(rows), dtype=torch.int64, device=d)
@@ -182,11 +202,11 @@ class DQNForward:
         q = torch.empty((B, self.num_actions), dtype=torch.float32, device=self.device)
         feat = torch.empty((B, 128), dtype=torch.float32, device=self.device) if features else None
         stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        check(self._L.snake_dqn_forward(ctypes.byref(self.cfg), ctypes.byref(self.net),
-                                        ctypes.c_void_p(obs.data_ptr()), B,
-                                        ctypes.c_void_p(self._scratch.data_ptr()),
-                                        ctypes.c_void_p(q.data_ptr()),
-                                        ctypes.c_void_p(feat.data_ptr()) if features else None, stream), self._L)
+        check(self._forward_fn(ctypes.byref(self.cfg), ctypes.byref(self.net),
+                               ctypes.c_void_p(obs.data_ptr()), B,
+                               ctypes.c_void_p(self._scratch.data_ptr()),
+                               ctypes.c_void_p(q.data_ptr()),
+                               ctypes.c_void_p(feat.data_ptr()) if features else None, stream), self._L)
         self._keep = obs
         return q, feat
 

@@ -108,8 +108,9 @@ def evaluate(env, qnet, steps, policy=None):
     """The vector form of DQN_Evaluator.evaluate (train_dqn.py:582-676): steps
     `env` (a SnakeVecEnv with all-done auto-reset) `steps` times with the
     safe-action rule on qnet's Q-values. qnet: any callable from uint8
-    (N*S, h, w, 8) observations to float32 (N*S, 3), e.g. DQNForward(...,
-    precision='fp32') on the 20x20 full map. A snake that is done gets action 0
+    (N*S, h, w, 8) observations to float32 (N*S, 3), e.g. DQNForward(...) on
+    the 20x20 full map (bf16 map path; precision='fp32' where the argmax has to
+    follow the reference's fp32 arithmetic bit for bit). A snake that is done gets action 0
     until its env's episode ends, and every episode starts with unknown
     directions, as in the reference.
 

@@ -4,7 +4,9 @@ hipBLASLt linears) in fp32 and bf16 on the same observations.
 
 The workload is one forward over the bench's observation batch: 65,536 envs x 4
 snakes = 262,144 observations of 11x11x8 (vision_range 5, frame_stack 1), the
-network of train_dqn.py:104-151 with random-init weights.
+network of train_dqn.py:104-151 with random-init weights. --vr 0 takes the full
+20x20 map (train_dqn.py's own Config; --envs 4096 is its batch of 16,384
+observations): fp32 mode, or the bf16 map path (--plan, --conv-waves).
 
 Algorithmic FLOP per observation (multiply-add = 2, unpadded shapes):
   conv_l: 2 * h*w * cout * 9*cin      fc: 2 * in * out
@@ -56,6 +58,8 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--no-torch', action='store_true')
     ap.add_argument('--precision', choices=('bf16', 'fp32'), default='bf16')
+    ap.add_argument('--plan', choices=('auto', 'window', 'map'), default='auto')
+    ap.add_argument('--conv-waves', type=int, default=0)
     args = ap.parse_args()
 
     from marlenv import SnakeVecEnv
@@ -74,14 +78,15 @@ def main():
     B, h, w, c = obs.shape
     del env
     ref = RefDQN(h, w, c, 3).cuda().eval()
-    net = DQNForward(ref, h, w, c, 3, precision=args.precision)
+    net = DQNForward(ref, h, w, c, 3, precision=args.precision, plan=args.plan, conv_waves=args.conv_waves)
     fpo = flops_per_obs(h, w, c, 3)
     peak = PEAK_BF16 if args.precision == 'bf16' else PEAK_FP32
 
     ms = timed(lambda: net(obs), args.steps, args.warmup)
     tf = fpo * B / (ms * 1e-3)
     out = {'metric': 'dqn_forward_obs_per_sec', 'value': B / (ms * 1e-3), 'unit': 'obs/s',
-           'ms_per_forward': ms, 'batch': B, 'obs_shape': [h, w, c],
+           'ms_per_forward': ms, 'batch': B, 'obs_shape': [h, w, c], 'plan': net.plan,
+           'conv_waves': args.conv_waves,
            'dtype': 'bf16 (fp32 accumulate)' if args.precision == 'bf16' else 'fp32',
            'flop_per_obs': fpo,
            'roofline': {'bound': 'mfma' if args.precision == 'bf16' else 'fp32 (vector = matrix peak)',

@@ -14,9 +14,9 @@ filler work so that the GPU never waits for the host inside a timed span.
 
 For scale, timed the same way in the same process: DQNForward.forward_features
 (random weights, observations of random 0/1 bytes) on the same number of rows
--- fp32 on train_ga.py's 20x20x8 full map, and the bf16 MFMA path on the 11x11x8
-crop it supports -- and one SnakeVecEnv.step of the same batch (20x20 board,
-full-map observations).
+-- fp32 and the bf16 map path on train_ga.py's 20x20x8 full map, and the bf16
+window path on the 11x11x8 crop -- and one SnakeVecEnv.step of the same batch
+(20x20 board, full-map observations).
 
 Prints one JSON record and writes it to profiles/genome_bench.json.
 """
@@ -95,7 +95,7 @@ def measure(N, populations, launches, warmup):
                      'scratch_tiles': int((tiles[:, 3] >= 0).sum()), 'lds_bytes': int(lay.lds_bytes),
                      'nodes_per_genome': [int(sizes.min()), int(sizes.max())],
                      'links': int(heads.cfg.num_links)}
-    for precision, side in (('fp32', 20), ('bf16', 11)):
+    for precision, side in (('fp32', 20), ('bf16', 20), ('bf16', 11)):
         obs = [torch.randint(0, 2, (N * S, side, side, 8), generator=gen, device='cuda', dtype=torch.uint8)
                for _ in range(4)]
         net = random_dqn(precision, side)
