@@ -367,6 +367,67 @@ int64_t snake_dqn32_scratch(const snake_dqn_cfg *cfg, int64_t batch);
 int snake_dqn32_forward(const snake_dqn_cfg *cfg, const snake_dqn32_net *net, const uint8_t *obs,
                         int64_t batch, void *scratch, float *q_out, float *feat_out, void *stream);
 
+/* ---- The learner: train_dqn.py's Trainer.update_model (:228-257) on the
+ * device, in fp32 (dqn_train_kernels.hip). No call below syncs with the host,
+ * no kernel uses a floating-point atomic: every sum has a fixed order that
+ * depends on the shapes alone, results are bitwise reproducible.
+ *
+ * snake_dqn32_backward: the gradients of sum(dq * Q) with respect to the twelve
+ * parameters, for the batch a preceding snake_dqn32_forward ran.
+ *   fwd_scratch    that forward's scratch (same cfg, obs, batch and weights): the
+ *                  pre-activations Y1..Y5 and the x.max() > 1 flag; read only
+ *   dq             float [B][A], any gradient with respect to the Q-values
+ *   train_scratch  snake_dqn32_train_scratch(cfg, batch) bytes, 16-byte aligned:
+ *                  dY5 [B][128] | dY4 [B][256] | dY3, dY2 [B*h*w][64] | dY1
+ *                  [B*h*w][32] (gradients with respect to the pre-activations,
+ *                  NHWC) | the weight-gradient partials | the bias partials
+ *   grad           a snake_dqn32_net whose twelve pointers are WRITTEN (the
+ *                  const is cast away): the weights' own layouts, i.e. conv
+ *                  [cout][(ky*3 + kx)*cin + ci], fc1 [256][p*64 + ch]; every
+ *                  element is overwritten, nothing accumulates across calls.
+ *                  Weights and gradients 16-byte aligned.
+ * A ReLU's mask is Y + bias > 0; conv1's weight gradient reads the uint8
+ * observation as the forward did (divided by 255 when the flag is set).
+ * Weight gradients dW[n][k] = sum_m dY[m][n] act(X)[m][k] and the convolutions'
+ * and fc1/fc2's input gradients run on the fp32 matrix cores on every geometry
+ * snake_dqn32_forward accepts (the conv input gradient in gather form); fc3 on
+ * the vector ALUs. Split M: the M = B*h*w (fc: B) rows of a weight or bias
+ * gradient are cut into chunks of max(2048, ceil(M/128) rounded up to 16) rows;
+ * with more than one chunk each writes a partial and a second kernel adds the
+ * partials in chunk order. batch in [0, 2^24]. */
+int64_t snake_dqn32_train_scratch(const snake_dqn_cfg *cfg, int64_t batch);   /* bytes, < 0 on error */
+int snake_dqn32_backward(const snake_dqn_cfg *cfg, const snake_dqn32_net *net, const uint8_t *obs,
+                         int64_t batch, const void *fwd_scratch, const float *dq, void *train_scratch,
+                         const snake_dqn32_net *grad, void *stream);
+
+/* The TD loss (:243-250), one launch. Per row b, in fp32 and in this order:
+ *   target = reward[b] + ((1 - done[b]) * gamma) * max_a next_q[b][a]
+ *   d      = q[b][action[b]] - target
+ * loss_out (one float) = (sum_b smooth_l1(d)) / B with smooth_l1(d) = 0.5 d^2
+ * for |d| < 1, else |d| - 0.5; dq [B][A] = clamp(d, -1, 1) / B at a = action[b],
+ * 0 elsewhere. q, next_q float [B][A]; action int64 [B]; reward, done float
+ * [B]. An action outside [0, A) is clamped into it and sets *err to 1 (err may
+ * be NULL; the caller zeroes it). batch in [1, 2^24], num_actions in [1, 64]. */
+int snake_dqn_td_loss(const float *q, const int64_t *action, const float *reward, const float *done,
+                      const float *next_q, int64_t batch, int32_t num_actions, float gamma,
+                      float *loss_out, float *dq, int32_t *err, void *stream);
+
+/* clip_grad_norm_(params, max_norm) then optim.Adam.step() (torch defaults: no
+ * amsgrad, no weight decay) over n elements; param, grad, exp_avg, exp_avg_sq
+ * are flat float [n] device buffers (padding elements hold zero gradients and
+ * stay unchanged). Three launches:
+ *   norm  = sqrt(sum g^2)            two-stage, fixed order; also to *norm_out
+ *   coef  = min(1, max_norm / (norm + 1e-6));  g' = g * coef  (grad is not written)
+ *   m     = beta1 m + (1 - beta1) g';  v = beta2 v + ((1 - beta2) g') g'
+ *   p     = p - step_size * (m / (sqrt(v) / sqrt(1 - beta2^step) + eps))
+ * with step_size = lr / (1 - beta1^step); the two corrections are computed on
+ * the host in double from the float arguments and rounded to float. step >= 1
+ * is the count including this step. scratch: SNAKE_ADAM_SCRATCH_BYTES. */
+#define SNAKE_ADAM_SCRATCH_BYTES 4112
+int snake_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
+                    int64_t step, float lr, float beta1, float beta2, float eps, float max_norm,
+                    void *scratch, float *norm_out, void *stream);
+
 /* ---- Safe-action selection: the action rule of the reference's evaluator
  * (train_dqn.py:433-580 DQN_Evaluator.get_action, driven by the loop at
  * :625-646) for every env at once. Per env the snakes are taken in index order

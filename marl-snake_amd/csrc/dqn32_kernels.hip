@@ -10,9 +10,10 @@
 // accumulation; gfx950's fp32 matrix and vector peaks are both 157 TF, the
 // matrix form needs far fewer issue slots): k_conv32_mfma for the convolutions
 // (A from an LDS patch of the input maps), k_fc32_mfma for fc1/fc2 (LDS-staged
-// tiles). k_gemm32, a 128x64-tile GEMM on the vector ALUs, runs fc3 (A <= 64
-// outputs) and the convolutions of maps too wide for the patch. The A operand is formed on
-// the fly (no im2col buffer):
+// tiles; up to 2 048 rows k_fc32_mfma_small, the same sums in 32 x 32 tiles,
+// bit-equal per row). k_gemm32, a 128x64-tile GEMM on the vector ALUs, runs
+// fc3 (A <= 64 outputs) and the convolutions of maps too wide for the patch.
+// The A operand is formed on the fly (no im2col buffer):
 //   kConvU8   conv1: m = (b, y, x), k = (tap, ci); X = the uint8 NHWC
 //             observation, zero outside the map (padding 1), / 255 when the
 //             batch holds a value > 1 (train_dqn.py:122: x / 255 if x.max() > 1)
@@ -32,25 +33,12 @@
 
 #include <algorithm>
 
-#include "snake_internal.h"
+#include "dqn32_shared.h"   // GemmArgs, the operand modes, check_cfg, Scratch, the patch sizes
 
 namespace snake {
 namespace dqn32 {
 
-enum { kConvU8 = 0, kConvF32 = 1, kDense = 2 };
 constexpr int BM = 128, BN = 64, BK = 16, kThreads = 256;
-struct GemmArgs {
-    const void *x;          // A source (see mode)
-    const float *xbias;     // bias applied (with ReLU) to the A source (modes 1, 2)
-    int bmod;               // bias period along k (mode 2)
-    const float *w;         // [N][K]
-    float *y;               // [M][N]
-    const float *ybias;     // added to the output (the last layer) or NULL
-    int64_t M;
-    int N, K;
-    int H, W, C;            // conv geometry (modes 0, 1): map H x W, input channels C
-    const int *scale_flag;  // mode 0: nonzero -> divide the uint8 input by 255
-};
 
 // One 128 x 64 output tile per 256-thread workgroup: thread (tx, ty) of 16 x 16
 // owns rows ty*4 .. +3 and 64 + ty*4 .. +3 and columns tx*4 .. +3 (32 fp32
@@ -211,29 +199,7 @@ __global__ void __launch_bounds__(kThreads) k_gemm32(const GemmArgs g)
 // (A: four consecutive channels of one cell) and one 16-byte global load (B: W
 // row-major [N][K]) feed four MFMAs. Output fragment: lane l, register r ->
 // row 4*(l/16)+r, column l%16.
-constexpr int kConvRows = 128;
-constexpr int kPatchMaxBytes = 80 * 1024;   // two workgroups per CU
-
-__host__ __device__ inline int conv_patch_rows(int H, int W)
-{
-    // tall rows spanned by 128 consecutive positions + the two halo rows
-    const int P = H * W;
-    return (kConvRows - 1 + W - 1) / W + 1 + (kConvRows - 1 + P - 1) / P + 2;
-}
-
-// Cell stride in floats: C + 8 when C % 16 == 0, else C (C % 8 == 0), so that the
-// stride in 16-byte slots is 2 mod 4. ds_read_b128 serves a wave in four lane
-// groups of 16 ({0-3,12-15,20-27}, {4-11,16-19,28-31}, and the upper half
-// alike: MI355X_MICROARCH.md §LDS); a group holds 8 rows of lane group g and
-// 8 of g+1, distinct mod 8, so their slots 2m*row + g are all distinct (a
-// stride of 1 mod 4 made every group 2-way).
-__host__ __device__ inline int conv_cell_stride(int C) { return C + ((C & 15) ? 0 : 8); }
-
-__host__ inline int64_t conv_patch_bytes(int H, int W, int C)
-{
-    return (int64_t)conv_patch_rows(H, W) * (W + 2) * conv_cell_stride(C) * 4;
-}
-
+// (kConvRows, the patch sizes and the cell stride: dqn32_shared.h)
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // NT = output channels / 16 (2: conv1, 4: conv2/conv3). Wave w takes column
@@ -533,10 +499,99 @@ __global__ void __launch_bounds__(512) k_fc32_mfma(const GemmArgs g)
         }
 }
 
+// The same layers at small batches (a learner's B = 512: k_fc32_mfma's grid for
+// fc1 would be 4 x 2 workgroups, each walking K = 64 h w alone): 32 x 32 tiles,
+// four waves of one 16 x 16 tile each, wave (rg, cg) = (w % 2, w / 2). Staging,
+// the k order inside a 32-k block and the MFMA sequence per output element are
+// k_fc32_mfma's, so every output has the same bits on either kernel.
+__global__ void __launch_bounds__(256) k_fc32_mfma_small(const GemmArgs g)
+{
+    __shared__ __attribute__((aligned(16))) float As[2][32 * kFcS];
+    __shared__ __attribute__((aligned(16))) float Bs[2][32 * kFcS];
+    __shared__ __attribute__((aligned(16))) float bias[256];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int rg = wave & 1, cg = wave >> 1, grp = lane >> 4, l16 = lane & 15;
+    const int K = g.K, N = g.N;
+    const int64_t M = g.M;
+    for (int q = tid; q < g.bmod; q += 256) bias[q] = g.xbias[q];
+    const int64_t m0 = (int64_t)blockIdx.x * 32;
+    const int n0 = blockIdx.y * 32;
+    // stager: thread t loads float4 (row t/8, k 4*(t%8)) of A and of W
+    const int sr = tid >> 3, sk = 4 * (tid & 7);
+    int64_t ms = m0 + sr;
+    if (ms >= M) ms = M - 1;   // computed, never stored
+    const float *ap = reinterpret_cast<const float *>(g.x) + ms * K + sk;
+    const float *wp = g.w + (int64_t)(n0 + sr) * K + sk;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    // kAhead blocks of global loads in flight (one block ahead, a wave spent a
+    // memory latency per 32-k block: 128 workgroups cannot hide it by occupancy);
+    // the loop is unrolled by kAhead so that the ring's slots are fixed registers
+    constexpr int kAhead = 4;
+    f32x4 ra[kAhead], rw[kAhead];
+    auto fetch = [&](int slot, int k0) {
+        const bool ok = k0 + sk < K;
+        ra[slot] = ok ? *reinterpret_cast<const f32x4 *>(ap + k0) : zero;
+        rw[slot] = ok ? *reinterpret_cast<const f32x4 *>(wp + k0) : zero;
+    };
+    const int bm = g.bmod - 1;
+    auto stage = [&](int buf, int slot, int k0) {
+        const f32x4 bv = *reinterpret_cast<const f32x4 *>(&bias[(k0 + sk) & bm]);
+        f32x4 a;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const float u = ra[slot][j] + bv[j];
+            a[j] = u > 0.f ? u : 0.f;   // (k past K: W is zero there)
+        }
+        *reinterpret_cast<f32x4 *>(&As[buf][sr * kFcS + sk]) = a;
+        *reinterpret_cast<f32x4 *>(&Bs[buf][sr * kFcS + sk]) = rw[slot];
+    };
+    f32x4 acc = zero;
+#pragma unroll
+    for (int u = 0; u < kAhead; u++) fetch(u, u * kFcK);   // (blocks past K: zeros, no load)
+    __syncthreads();   // bias
+    stage(0, 0, 0);
+    fetch(0, kAhead * kFcK);
+    __syncthreads();
+    const int nb = (K + kFcK - 1) / kFcK;
+    for (int kb0 = 0; kb0 < nb; kb0 += kAhead) {
+#pragma unroll
+        for (int u = 0; u < kAhead; u++) {
+            const int kb = kb0 + u;
+            if (kb >= nb) break;   // (uniform)
+            const int cur = u & 1;   // kb & 1: kAhead is even
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const f32x4 a = *reinterpret_cast<const f32x4 *>(&As[cur][(rg * 16 + l16) * kFcS + 16 * h + 4 * grp]);
+                const f32x4 b = *reinterpret_cast<const f32x4 *>(&Bs[cur][(cg * 16 + l16) * kFcS + 16 * h + 4 * grp]);
+#pragma unroll
+                for (int j = 0; j < 4; j++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b[j], acc, 0, 0, 0);
+            }
+            if (kb + 1 < nb) {
+                const int slot = (u + 1) % kAhead;   // block kb + 1's registers
+                stage(cur ^ 1, slot, (kb + 1) * kFcK);
+                fetch(slot, (kb + 1 + kAhead) * kFcK);
+            }
+            __syncthreads();
+        }
+    }
+    const int n = n0 + cg * 16 + l16;
+    const float yb = g.ybias ? g.ybias[n] : 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int64_t m = m0 + rg * 16 + 4 * grp + r;
+        if (m < M) g.y[m * N + n] = acc[r] + yb;
+    }
+}
+
+constexpr int64_t kFcSmallRows = 2048;   // up to this many rows: k_fc32_mfma_small
+
 int fc_mfma(const GemmArgs &g, hipStream_t s, const char *what)
 {
     const dim3 grid((unsigned)((g.M + 127) / 128), (unsigned)(g.N / 128));
-    hipLaunchKernelGGL(k_fc32_mfma, grid, dim3(512), 0, s, g);
+    if (g.M <= kFcSmallRows)
+        hipLaunchKernelGGL(k_fc32_mfma_small, dim3((unsigned)((g.M + 31) / 32), (unsigned)(g.N / 32)), dim3(256), 0, s, g);
+    else
+        hipLaunchKernelGGL(k_fc32_mfma, grid, dim3(512), 0, s, g);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) { set_error("%s launch failed: %s", what, hipGetErrorString(err)); return SNAKE_E_LAUNCH; }
     return SNAKE_OK;
@@ -569,46 +624,6 @@ int gemm(const GemmArgs &g, hipStream_t s, const char *what)
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) { set_error("%s launch failed: %s", what, hipGetErrorString(err)); return SNAKE_E_LAUNCH; }
     return SNAKE_OK;
-}
-
-int check_cfg(const snake_dqn_cfg *cfg)
-{
-    if (!cfg) { set_error("snake_dqn32: NULL cfg"); return SNAKE_E_ARG; }
-    if (cfg->height < 1 || cfg->width < 1 || cfg->height > 255 || cfg->width > 255) {
-        set_error("snake_dqn32: observation %dx%d out of range", cfg->height, cfg->width);
-        return SNAKE_E_CONFIG;
-    }
-    if (cfg->channels < 8 || cfg->channels % 8 || cfg->channels > 128) {
-        set_error("snake_dqn32: channels must be a multiple of 8 in [8, 128] (got %d)", cfg->channels);
-        return SNAKE_E_CONFIG;
-    }
-    if (cfg->num_actions < 1 || cfg->num_actions > 64) {
-        set_error("snake_dqn32: num_actions must be in [1, 64] (got %d)", cfg->num_actions);
-        return SNAKE_E_CONFIG;
-    }
-    return SNAKE_OK;
-}
-
-// scratch layout (bytes): flag (16) | Y1 | Y2 | Y3 | Y4 | Y5
-struct Scratch {
-    int *flag;
-    float *y1, *y2, *y3, *y4, *y5;
-};
-
-int64_t scratch_bytes(const snake_dqn_cfg *cfg, int64_t B, void *base, Scratch *out)
-{
-    const int64_t P = (int64_t)cfg->height * cfg->width;
-    const int64_t n1 = B * P * 32, n2 = B * P * 64, n3 = n2, n4 = B * 256, n5 = B * 128;
-    if (out) {
-        uint8_t *p = reinterpret_cast<uint8_t *>(base);
-        out->flag = reinterpret_cast<int *>(p);
-        out->y1 = reinterpret_cast<float *>(p + 16);
-        out->y2 = out->y1 + n1;
-        out->y3 = out->y2 + n2;
-        out->y4 = out->y3 + n3;
-        out->y5 = out->y4 + n4;
-    }
-    return 16 + 4 * (n1 + n2 + n3 + n4 + n5);
 }
 
 }  // namespace dqn32

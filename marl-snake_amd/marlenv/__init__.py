@@ -10,6 +10,7 @@ from .vec_env import SnakeVecEnv  # noqa: F401
 from .dqn import DQNForward  # noqa: F401
 from .policy import SafeActions, evaluate  # noqa: F401
 from .replay import Collector, ReplayBuffer  # noqa: F401
+from .learner import DQNLearner  # noqa: F401
 from .neat_head import GenomeHeads, evaluate_population  # noqa: F401
 from .arena import GreedyActions, HybridNEAT, SafeDQN, battle  # noqa: F401
 from .graph import GraphObs, GraphVecEnv  # noqa: F401

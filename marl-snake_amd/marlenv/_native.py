@@ -20,7 +20,10 @@ EXPORTS = ('snake_plan', 'snake_plan_paths', 'snake_build_candidates', 'snake_se
            'snake_policy_plan', 'snake_safe_actions', 'snake_greedy_actions',
            'snake_replay_plan', 'snake_replay_push', 'snake_replay_gather',
            'snake_genome_plan', 'snake_genome_check', 'snake_genome_tiles', 'snake_genome_actions',
-           'snake_graph_plan', 'snake_graph_weights', 'snake_graph_obs')
+           'snake_graph_plan', 'snake_graph_weights', 'snake_graph_obs',
+           'snake_dqn32_train_scratch', 'snake_dqn32_backward', 'snake_dqn_td_loss', 'snake_adam_step')
+
+ADAM_SCRATCH_BYTES = 4112       # SNAKE_ADAM_SCRATCH_BYTES
 
 
 class SnakeCfg(ctypes.Structure):
@@ -179,6 +182,13 @@ def lib(path=None):
     L.snake_dqn32_scratch.argtypes = [ctypes.POINTER(DqnCfg), I64]
     L.snake_dqn32_scratch.restype = I64
     L.snake_dqn32_forward.argtypes = [ctypes.POINTER(DqnCfg), ctypes.POINTER(Dqn32Net), P, I64, P, P, P, P]
+    L.snake_dqn32_train_scratch.argtypes = [ctypes.POINTER(DqnCfg), I64]
+    L.snake_dqn32_train_scratch.restype = I64
+    L.snake_dqn32_backward.argtypes = [ctypes.POINTER(DqnCfg), ctypes.POINTER(Dqn32Net), P, I64, P, P, P,
+                                       ctypes.POINTER(Dqn32Net), P]
+    F32 = ctypes.c_float
+    L.snake_dqn_td_loss.argtypes = [P, P, P, P, P, I64, ctypes.c_int32, F32, P, P, P, P]
+    L.snake_adam_step.argtypes = [P, P, P, P, I64, I64, F32, F32, F32, F32, F32, P, P, P]
     L.snake_policy_plan.argtypes = [ctypes.POINTER(PolicyCfg)]
     L.snake_safe_actions.argtypes = [ctypes.POINTER(PolicyCfg), P, P, P, P, P, I64, P]
     L.snake_greedy_actions.argtypes = [ctypes.POINTER(PolicyCfg), P, P, P, P, P, I64, P]

@@ -1,0 +1,296 @@
+"""The reference trainer's gradient step on the GPU.
+
+train_dqn.py's Trainer.update_model (:228-257) runs once per env step: Q(s, a)
+from the policy net, max Q(s', .) from the target net, smooth-L1 loss,
+backward, clip_grad_norm_(10) and optim.Adam.step(). DQNLearner is that step in
+fp32 on the device: the forward of dqn32_kernels.hip, and the backward pass, TD
+loss and clip + Adam of dqn_train_kernels.hip (snake_dqn32_backward,
+snake_dqn_td_loss, snake_adam_step; the exact semantics are in
+include/snake_env.h). Nothing in update() syncs with the host.
+
+The master weights are the fp32 kernels' own layouts (snake_dqn32_net), so
+acting, the target forward and the update need no repacking: parameters,
+gradients and Adam's m and v are one flat float32 buffer each, the twelve
+tensors views into it at offsets padded to 64 bytes; the target net is a second
+flat buffer. state_dict(), grads() and checkpoint() convert to the reference's
+names and layouts with torch ops, off the hot path.
+"""
+import ctypes
+
+from ._device import get_torch as _torch, ptr, stream_ptr
+from ._native import ADAM_SCRATCH_BYTES, Dqn32Net, DqnCfg, check, lib
+from .dqn import _check_shapes
+
+# snake_dqn32_net's field order, with the reference's parameter names
+FIELDS = ('conv1_w', 'conv2_w', 'conv3_w', 'fc1_w', 'fc2_w', 'fc3_w',
+          'conv1_b', 'conv2_b', 'conv3_b', 'fc1_b', 'fc2_b', 'fc3_b')
+NAMES = tuple(f[:-2] + ('.weight' if f.endswith('_w') else '.bias') for f in FIELDS)
+PAD = 16        # floats: every tensor starts at a multiple of 64 bytes
+
+
+def kernel_shapes(P, C, A):
+    """The twelve tensors' shapes in the kernel layouts, in FIELDS order."""
+    return ((32, 9 * C), (64, 288), (64, 576), (256, 64 * P), (128, 256), (A, 128),
+            (32,), (64,), (64,), (256,), (128,), (A,))
+
+
+def to_kernel(name, t, P):
+    """A reference-layout tensor (conv [out][in][3][3], fc1 columns ch*P + p) in
+    the kernel layout (conv [out][(tap, ci)], fc1 columns p*64 + ch)."""
+    if name.startswith('conv') and t.dim() == 4:
+        return t.permute(0, 2, 3, 1).reshape(t.shape[0], -1)
+    if name == 'fc1.weight':
+        return t.reshape(256, 64, P).permute(0, 2, 1).reshape(256, P * 64)
+    return t
+
+
+def from_kernel(name, t, P):
+    """The inverse of to_kernel (a new contiguous tensor)."""
+    if name.startswith('conv') and t.dim() == 2:
+        return t.reshape(t.shape[0], 3, 3, -1).permute(0, 3, 1, 2).contiguous()
+    if name == 'fc1.weight':
+        return t.reshape(256, P, 64).permute(0, 2, 1).reshape(256, 64 * P).contiguous()
+    return t.clone()
+
+
+class DQNLearner:
+    """Trainer.update_model on the device.
+
+    state: a state dict (or nn.Module) of the reference DQN; both the policy and
+    the target net start from it. height, width, channels: the observation
+    (anything snake_dqn32_forward accepts). lr, betas, eps: optim.Adam's;
+    gamma: the discount; max_grad_norm: clip_grad_norm_'s bound.
+
+    learner(obs) / forward_features(obs): the policy net on uint8 (B, h, w, C)
+    observations; target_q(obs): the target net. update(*buf.sample(B)) is one
+    gradient step and returns the loss as a float32 () tensor on the device.
+    The stages of update() are methods of their own: td_loss, backward (for
+    the observations of the last policy forward), apply; grads() and grad_norm
+    show what they left."""
+
+    def __init__(self, state, height, width, channels, num_actions=3, lr=5e-4, gamma=0.99, betas=(0.9, 0.999),
+                 eps=1e-8, max_grad_norm=10.0, device=None, lib_path=None):
+        torch = _torch()
+        if hasattr(state, 'state_dict'):
+            state = state.state_dict()
+        H, W, C, A = int(height), int(width), int(channels), int(num_actions)
+        self._L = L = lib(lib_path)
+        self.cfg = DqnCfg(H, W, C, A, 0)
+        n = L.snake_dqn32_train_scratch(ctypes.byref(self.cfg), 0)      # ValueError before any device work
+        check(int(n) if n < 0 else 0, L)
+        _check_shapes(state, C, H * W, A)
+        if not (lr > 0.0 and eps >= 0.0 and max_grad_norm > 0.0 and 0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError('lr and max_grad_norm must be positive, eps >= 0, betas in [0, 1)')
+        self.lr, self.gamma, self.betas, self.eps = float(lr), float(gamma), (float(betas[0]), float(betas[1])), float(eps)
+        self.max_grad_norm = float(max_grad_norm)
+        self.obs_shape = (H, W, C)
+        self.num_actions = A
+        self._P = P = H * W
+        if not torch.cuda.is_available():
+            raise RuntimeError('DQNLearner needs a HIP device (MI355X); there is no CPU fallback')
+        dev = torch.device(device) if device is not None else torch.device('cuda')
+        if dev.index is None:
+            dev = torch.device('cuda', torch.cuda.current_device())
+        self.device = dev
+        self._shapes = kernel_shapes(P, C, A)
+        self._offsets, off = [], 0
+        for shape in self._shapes:
+            self._offsets.append(off)
+            size = shape[0] * (shape[1] if len(shape) == 2 else 1)
+            off += (size + PAD - 1) // PAD * PAD
+        self.numel = off
+
+        def flat():
+            return torch.zeros(self.numel, dtype=torch.float32, device=dev)
+
+        self._param, self._target, self._grad, self._m, self._v = flat(), flat(), flat(), flat(), flat()
+        self._net, self._tnet, self._gnet = (self._struct(b) for b in (self._param, self._target, self._grad))
+        self.step = 0
+        self.grad_norm = torch.zeros((), dtype=torch.float32, device=dev)
+        self.err = torch.zeros(1, dtype=torch.int32, device=dev)        # 1 once td_loss clamped an action
+        self._adam_scratch = torch.zeros(ADAM_SCRATCH_BYTES, dtype=torch.uint8, device=dev)
+        self._scratch = {}          # 'policy' / 'target' / 'train' -> uint8 buffers
+        self._fwd = None            # (obs, B) of the last policy forward
+        self._keep = None
+        self._load(self._param, state)
+        self.sync_target()
+
+    # ------------------------------------------------------------ flat buffers
+    def _views(self, buf):
+        out = {}
+        for name, shape, off in zip(NAMES, self._shapes, self._offsets):
+            size = shape[0] * (shape[1] if len(shape) == 2 else 1)
+            out[name] = buf[off:off + size].view(shape)
+        return out
+
+    def _struct(self, buf):
+        base = buf.data_ptr()
+        return Dqn32Net(*(base + 4 * off for off in self._offsets))
+
+    def _load(self, buf, state):
+        torch = _torch()
+        _check_shapes(state, self.obs_shape[2], self._P, self.num_actions)
+        for name, view in self._views(buf).items():
+            t = state[name].detach().to(device=self.device, dtype=torch.float32)
+            view.copy_(to_kernel(name, t, self._P))
+
+    def _unpack(self, buf):
+        return {name: from_kernel(name, view, self._P) for name, view in self._views(buf).items()}
+
+    def _buffer(self, key, nbytes):
+        torch = _torch()
+        buf = self._scratch.get(key)
+        if buf is None or buf.numel() < nbytes:
+            buf = self._scratch[key] = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=self.device)
+        return buf
+
+    # ----------------------------------------------------------------- forward
+    def _check_obs(self, obs, who):
+        torch = _torch()
+        if not isinstance(obs, torch.Tensor) or obs.dtype != torch.uint8 or not obs.is_contiguous():
+            raise TypeError('DQNLearner.%s takes the observations as a contiguous uint8 tensor' % who)
+        if obs.dim() != 4 or tuple(obs.shape[1:]) != self.obs_shape:
+            raise ValueError('observations shape %s is not (B,) + %s' % (tuple(obs.shape), self.obs_shape))
+        if obs.device != self.device:
+            raise ValueError('observations are on %s, this DQNLearner on %s' % (obs.device, self.device))
+        return obs.shape[0]
+
+    def _forward(self, net, key, obs, features, who):
+        torch = _torch()
+        B = self._check_obs(obs, who)
+        need = int(self._L.snake_dqn32_scratch(ctypes.byref(self.cfg), B))
+        check(need if need < 0 else 0, self._L)
+        scratch = self._buffer(key, need)
+        q = torch.empty((B, self.num_actions), dtype=torch.float32, device=self.device)
+        feat = torch.empty((B, 128), dtype=torch.float32, device=self.device) if features else None
+        with torch.cuda.device(self.device):
+            check(self._L.snake_dqn32_forward(ctypes.byref(self.cfg), ctypes.byref(net), ptr(obs), B, ptr(scratch),
+                                              ptr(q), ptr(feat), stream_ptr(self.device)), self._L)
+        if key == 'policy':
+            self._fwd = (obs, B)
+        return q, feat
+
+    def __call__(self, obs):
+        """The policy net's Q-values: uint8 (B, h, w, C) -> float32 (B, A)."""
+        return self._forward(self._net, 'policy', obs, False, '__call__')[0]
+
+    def forward_features(self, obs):
+        """The policy net's relu(fc2): float32 (B, 128)."""
+        return self._forward(self._net, 'policy', obs, True, 'forward_features')[1]
+
+    def target_q(self, obs):
+        """The target net's Q-values."""
+        return self._forward(self._tnet, 'target', obs, False, 'target_q')[0]
+
+    # ------------------------------------------------------------------ stages
+    def td_loss(self, q, action, reward, done, next_q):
+        """(loss, dq): the smooth-L1 loss of q[b][action[b]] against reward +
+        (1 - done) * gamma * max next_q, float32 (), and its gradient with
+        respect to q, float32 (B, A). q, next_q: float32 (B, A); action: int64
+        (B,); reward, done: float32 (B,). An action outside [0, A) is clamped
+        and sets self.err."""
+        torch = _torch()
+        A = self.num_actions
+        if not isinstance(q, torch.Tensor) or q.dtype != torch.float32:
+            raise TypeError('DQNLearner.td_loss takes q as a float32 tensor (got %s)' % getattr(q, 'dtype', type(q)))
+        if q.dim() != 2 or q.shape[1] != A:
+            raise ValueError('q shape %s is not (B, %d)' % (tuple(q.shape), A))
+        B = q.shape[0]
+        if B < 1:
+            raise ValueError('td_loss needs at least one row')
+        for name, t, dtype, shape in (('action', action, torch.int64, (B,)), ('reward', reward, torch.float32, (B,)),
+                                      ('done', done, torch.float32, (B,)), ('next_q', next_q, torch.float32, (B, A))):
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+                raise TypeError('DQNLearner.td_loss takes %s as a %s tensor (got %s)' % (
+                    name, dtype, getattr(t, 'dtype', type(t))))
+            if tuple(t.shape) != shape:
+                raise ValueError('%s shape %s is not %s' % (name, tuple(t.shape), shape))
+        for name, t in (('q', q), ('action', action), ('reward', reward), ('done', done), ('next_q', next_q)):
+            if t.device != self.device:
+                raise ValueError('%s is on %s, this DQNLearner on %s' % (name, t.device, self.device))
+        q, action, reward, done, next_q = (t.contiguous() for t in (q, action, reward, done, next_q))
+        loss = torch.empty((), dtype=torch.float32, device=self.device)
+        dq = torch.empty((B, A), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self._L.snake_dqn_td_loss(ptr(q), ptr(action), ptr(reward), ptr(done), ptr(next_q), B, A,
+                                            self.gamma, ptr(loss), ptr(dq), ptr(self.err),
+                                            stream_ptr(self.device)), self._L)
+        self._keep = (q, action, reward, done, next_q)
+        return loss, dq
+
+    def backward(self, obs, dq):
+        """The gradients of sum(dq * Q(obs)) into the gradient buffer. obs must be
+        the tensor of the last policy forward (its scratch is what is read)."""
+        torch = _torch()
+        B = self._check_obs(obs, 'backward')
+        if self._fwd is None or self._fwd[0] is not obs or self._fwd[1] != B:
+            raise ValueError('backward needs the observations of the last policy forward (call learner(obs) first)')
+        if not isinstance(dq, torch.Tensor) or dq.dtype != torch.float32:
+            raise TypeError('DQNLearner.backward takes dq as a float32 tensor')
+        if tuple(dq.shape) != (B, self.num_actions):
+            raise ValueError('dq shape %s is not %s' % (tuple(dq.shape), (B, self.num_actions)))
+        if dq.device != self.device:
+            raise ValueError('dq is on %s, this DQNLearner on %s' % (dq.device, self.device))
+        dq = dq.contiguous()
+        need = int(self._L.snake_dqn32_train_scratch(ctypes.byref(self.cfg), B))
+        check(need if need < 0 else 0, self._L)
+        ts = self._buffer('train', need)
+        with torch.cuda.device(self.device):
+            check(self._L.snake_dqn32_backward(ctypes.byref(self.cfg), ctypes.byref(self._net), ptr(obs), B,
+                                               ptr(self._scratch['policy']), ptr(dq), ptr(ts),
+                                               ctypes.byref(self._gnet), stream_ptr(self.device)), self._L)
+        self._keep_dq = dq
+
+    def apply(self):
+        """clip_grad_norm_ and one Adam step from the gradient buffer; the norm
+        before clipping goes to self.grad_norm."""
+        torch = _torch()
+        self.step += 1
+        with torch.cuda.device(self.device):
+            check(self._L.snake_adam_step(ptr(self._param), ptr(self._grad), ptr(self._m), ptr(self._v), self.numel,
+                                          self.step, self.lr, self.betas[0], self.betas[1], self.eps,
+                                          self.max_grad_norm, ptr(self._adam_scratch), ptr(self.grad_norm),
+                                          stream_ptr(self.device)), self._L)
+
+    def update(self, state, action, reward, next_state, done):
+        """update_model on ReplayBuffer.sample(format='uint8')'s five tensors;
+        returns the loss, float32 () on the device. No host sync."""
+        next_q = self.target_q(next_state)
+        q = self(state)
+        loss, dq = self.td_loss(q, action, reward, done, next_q)
+        self.backward(state, dq)
+        self.apply()
+        return loss
+
+    # ------------------------------------------------------------------- state
+    def sync_target(self):
+        """target_net.load_state_dict(policy_net.state_dict())."""
+        self._target.copy_(self._param)
+
+    def state_dict(self):
+        """The policy net with the reference's names and layouts (copies)."""
+        return self._unpack(self._param)
+
+    def target_state_dict(self):
+        return self._unpack(self._target)
+
+    def grads(self):
+        """The gradient buffer in the reference's layout (what .grad holds
+        after loss.backward(), before the clip)."""
+        return self._unpack(self._grad)
+
+    def checkpoint(self):
+        """The learner's part of the reference's save_checkpoint (:356-383): both
+        nets and Adam's state (step, exp_avg, exp_avg_sq by parameter name)."""
+        return {'policy_net': self.state_dict(), 'target_net': self.target_state_dict(),
+                'optimizer': {'step': self.step, 'exp_avg': self._unpack(self._m),
+                              'exp_avg_sq': self._unpack(self._v)}}
+
+    def load_checkpoint(self, ckpt):
+        opt = ckpt['optimizer']
+        self._load(self._param, ckpt['policy_net'])
+        self._load(self._target, ckpt['target_net'])
+        self._load(self._m, opt['exp_avg'])
+        self._load(self._v, opt['exp_avg_sq'])
+        self.step = int(opt['step'])
+        self._fwd = None
