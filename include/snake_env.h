@@ -428,6 +428,40 @@ int snake_adam_step(float *param, const float *grad, float *exp_avg, float *exp_
                     int64_t step, float lr, float beta1, float beta2, float eps, float max_norm,
                     void *scratch, float *norm_out, void *stream);
 
+/* ---- The learner's weights in the bf16 forward's layouts (dqn_pack_kernels.hip):
+ * a device-side conversion, so that a training loop acts (and forms its targets)
+ * with snake_dqn_forward / snake_dqn_map_forward on the weights it is training.
+ *   cfg, map_plan  the geometry and the plan whose layouts dst receives: 0 the
+ *                  window plan (snake_dqn_plan), 1 the map plan
+ *                  (snake_dqn_map_plan). Whatever that plan rejects is
+ *                  SNAKE_E_CONFIG with the plan's message, before any launch.
+ *   src            a net in the fp32 layouts above: conv [out][(ky*3 + kx)*cin +
+ *                  ci], fc1 columns p*64 + ch, fc2 and fc3 row-major; read only
+ *   dst            a snake_dqn_net whose twelve pointers are WRITTEN (the const
+ *                  is cast away), sized by the plan's snake_dqn_layout: the conv
+ *                  weights in MFMA fragment order, zero for channels in [C, cpad)
+ *                  and for k in [9*cpad, k1); fc1 [256][64*p16] in conv3's
+ *                  fragment order, zero in the GEMM rows whose rows[i] is -1 (or
+ *                  anything else outside [0, h*w)); fc2 [128][256]; the five
+ *                  biases, fc3_w and fc3_b copied as fp32. Every element of every
+ *                  destination is written on every call: a packed net is a
+ *                  snapshot of src, whatever the buffers held before.
+ *   rows           p16 entries, the plan's own table (snake_dqn_rows /
+ *                  snake_dqn_map_rows), in device memory
+ * fp32 -> bf16 rounds to nearest even on the bit pattern, (u + 0x7fff + ((u >>
+ * 16) & 1)) >> 16, as the forward rounds its activations; a NaN stays a NaN (its
+ * bits are not pinned). src and dst must not overlap; the five weight tensors of
+ * both are 16-byte aligned. One launch (k_dqn_pack) on `stream`, on the stream's
+ * device; no atomics, no host sync.
+ *
+ * snake_dqn_pack32_host: the same conversion with every pointer a host pointer
+ * (no alignment rule), as plain loops over the index mappings the kernel uses;
+ * no device needed. */
+int snake_dqn_pack32(const snake_dqn_cfg *cfg, int32_t map_plan, const snake_dqn32_net *src,
+                     const snake_dqn_net *dst, const int32_t *rows, void *stream);
+int snake_dqn_pack32_host(const snake_dqn_cfg *cfg, int32_t map_plan, const snake_dqn32_net *src,
+                          const snake_dqn_net *dst, const int32_t *rows);
+
 /* ---- Safe-action selection: the action rule of the reference's evaluator
  * (train_dqn.py:433-580 DQN_Evaluator.get_action, driven by the loop at
  * :625-646) for every env at once. Per env the snakes are taken in index order

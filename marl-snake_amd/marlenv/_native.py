@@ -21,7 +21,8 @@ EXPORTS = ('snake_plan', 'snake_plan_paths', 'snake_build_candidates', 'snake_se
            'snake_replay_plan', 'snake_replay_push', 'snake_replay_gather',
            'snake_genome_plan', 'snake_genome_check', 'snake_genome_tiles', 'snake_genome_actions',
            'snake_graph_plan', 'snake_graph_weights', 'snake_graph_obs',
-           'snake_dqn32_train_scratch', 'snake_dqn32_backward', 'snake_dqn_td_loss', 'snake_adam_step')
+           'snake_dqn32_train_scratch', 'snake_dqn32_backward', 'snake_dqn_td_loss', 'snake_adam_step',
+           'snake_dqn_pack32', 'snake_dqn_pack32_host')
 
 ADAM_SCRATCH_BYTES = 4112       # SNAKE_ADAM_SCRATCH_BYTES
 
@@ -189,6 +190,9 @@ def lib(path=None):
     F32 = ctypes.c_float
     L.snake_dqn_td_loss.argtypes = [P, P, P, P, P, I64, ctypes.c_int32, F32, P, P, P, P]
     L.snake_adam_step.argtypes = [P, P, P, P, I64, I64, F32, F32, F32, F32, F32, P, P, P]
+    L.snake_dqn_pack32.argtypes = [ctypes.POINTER(DqnCfg), ctypes.c_int32, ctypes.POINTER(Dqn32Net),
+                                   ctypes.POINTER(DqnNet), P, P]
+    L.snake_dqn_pack32_host.argtypes = L.snake_dqn_pack32.argtypes[:5]
     L.snake_policy_plan.argtypes = [ctypes.POINTER(PolicyCfg)]
     L.snake_safe_actions.argtypes = [ctypes.POINTER(PolicyCfg), P, P, P, P, P, I64, P]
     L.snake_greedy_actions.argtypes = [ctypes.POINTER(PolicyCfg), P, P, P, P, P, I64, P]

@@ -16,7 +16,9 @@ reference's own 20x20 full map); both feed the same fc kernel. The weights
 come from a state dict with the reference's parameter names (conv1.weight, ...,
 fc3.bias) and are packed once into the kernel layouts (include/snake_env.h
 snake_dqn_layout); packing is a layout transform done with torch ops, the
-forward pass is the HIP kernels only.
+forward pass is the HIP kernels only. A forward that follows weights in
+training is made empty and packed on the device instead (DQNForward.empty,
+pack32: dqn_pack_kernels.hip), with no host sync.
 """
 import ctypes
 
@@ -50,6 +52,22 @@ def _check_shapes(state, C, P, A):
             raise ValueError('%s shape %s != %s' % (name, got, shape))
 
 
+NET_FIELDS = tuple(n for n, _ in DqnNet._fields_)     # snake_dqn_net's field order
+
+
+def bf16_plan(L, cfg, plan='auto'):
+    """(plan name, DqnLayout) of the bf16 forward for a DqnCfg: 'auto' is the
+    window plan where it accepts the geometry, else the map plan. Host only;
+    ValueError with the plan's message where the chosen plan rejects cfg."""
+    if plan not in ('auto', 'window', 'map'):
+        raise ValueError("plan must be 'auto', 'window' or 'map'")
+    lay = DqnLayout()
+    if plan == 'auto':
+        plan = 'window' if L.snake_dqn_plan(ctypes.byref(cfg), ctypes.byref(lay)) == 0 else 'map'
+    check((L.snake_dqn_plan if plan == 'window' else L.snake_dqn_map_plan)(ctypes.byref(cfg), ctypes.byref(lay)), L)
+    return plan, lay
+
+
 class DQNForward:
     """DQN(input_shape=(N, h, w, c), num_actions) forward on uint8 NHWC observations.
 
@@ -61,7 +79,11 @@ class DQNForward:
     4), 'map' (any h x w with (h+2)*(w+2) <= 576, e.g. train_dqn.py's 20x20
     full-map Config; conv_waves in MAP_CONV_WAVES) or 'auto' (window where it
     accepts the geometry, else map). The plan in use is self.plan (None in
-    fp32 mode)."""
+    fp32 mode).
+
+    DQNForward.empty(...) makes a bf16 forward without a state dict, whose
+    buffers pack32() fills on the device from fp32 master weights
+    (snake_dqn_pack32): what DQNLearner.actor() returns."""
 
     def __init__(self, state, height, width, channels, num_actions=3, device=None, lib_path=None, conv_waves=0,
                  precision='bf16', plan='auto'):
@@ -149,6 +171,67 @@ class DQNForward:
             'fc2_b', 'fc3_w', 'fc3_b')))
         self.num_actions = A
         self._scratch = None
+
+    @classmethod
+    def empty(cls, height, width, channels, num_actions=3, device=None, plan='auto', conv_waves=0, lib_path=None):
+        """A bf16 DQNForward with allocated weight buffers and no state dict: the
+        buffers hold nothing until pack32() fills them (DQNLearner.actor() does).
+        The plan's row table is uploaded here, once. Where no bf16 plan accepts
+        the geometry this raises ValueError with the plan's message, before any
+        device work. Like every bf16 forward it reads the observations as 0/1
+        bytes: the reference's /255 branch is not taken."""
+        torch = _torch()
+        self = cls.__new__(cls)
+        self._L = L = lib(lib_path)
+        self.cfg = DqnCfg(int(height), int(width), int(channels), int(num_actions), int(conv_waves))
+        self.precision = 'bf16'
+        lay_name, lay = bf16_plan(L, self.cfg, plan)
+        self.plan, self.layout = lay_name, lay
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        self.num_actions = A = int(num_actions)
+        rows_fn, self._forward_fn = ((L.snake_dqn_rows, L.snake_dqn_forward) if lay_name == 'window' else
+                                     (L.snake_dqn_map_rows, L.snake_dqn_map_forward))
+        rows = (ctypes.c_int32 * lay.p16)()
+        n = rows_fn(ctypes.byref(self.cfg), ctypes.cast(rows, ctypes.c_void_p), lay.p16)
+        if n != lay.p16:
+            check(int(n) if n < 0 else -1, L)
+        d = self.device
+        self._rows = torch.tensor(list(rows), dtype=torch.int32, device=d)
+        sizes = (('conv1_w', lay.conv1_w), ('conv2_w', lay.conv2_w), ('conv3_w', lay.conv3_w), ('fc1_w', lay.fc1_w),
+                 ('fc2_w', lay.fc2_w))
+        self.tensors = {k: torch.empty(int(n), dtype=torch.int16, device=d) for k, n in sizes}
+        for k, shape in (('conv1_b', (32,)), ('conv2_b', (64,)), ('conv3_b', (64,)), ('fc1_b', (256,)),
+                         ('fc2_b', (128,)), ('fc3_w', (A, 128)), ('fc3_b', (A,))):
+            self.tensors[k] = torch.empty(shape, dtype=torch.float32, device=d)
+        self.net = DqnNet(*(self.tensors[k].data_ptr() for k in NET_FIELDS))
+        self._scratch = None
+        self._source = None
+        return self
+
+    def pack32(self, net32):
+        """Overwrite every weight buffer from a net in the fp32 kernels' layouts
+        (a _native.Dqn32Net of pointers on this forward's device): one launch of
+        snake_dqn_pack32 on the current stream, no host sync, no allocation. On
+        device='cpu' the library's host twin runs instead. Only forwards made by
+        DQNForward.empty() have the row table this needs."""
+        torch = _torch()
+        rows = getattr(self, '_rows', None)
+        if rows is None:
+            raise ValueError('pack32 needs a DQNForward made by DQNForward.empty()')
+        args = (ctypes.byref(self.cfg), 0 if self.plan == 'window' else 1, ctypes.byref(net32), ctypes.byref(self.net),
+                ctypes.c_void_p(rows.data_ptr()))
+        if self.device.type != 'cuda':
+            check(self._L.snake_dqn_pack32_host(*args), self._L)
+            return
+        with torch.cuda.device(self.device):
+            stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            check(self._L.snake_dqn_pack32(*(args + (stream,))), self._L)
+
+    def sync(self):
+        """Repack from the learner this forward is an actor of (DQNLearner.actor())."""
+        if getattr(self, '_source', None) is None:
+            raise ValueError('sync() needs a DQNForward made by DQNLearner.actor()')
+        self._source.sync_actor(self)
 
     def _init_fp32(self, state):
         """fp32 weights, row-major [out][in] (include/snake_env.h snake_dqn32_net);

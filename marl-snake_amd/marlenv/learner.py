@@ -14,12 +14,17 @@ gradients and Adam's m and v are one flat float32 buffer each, the twelve
 tensors views into it at offsets padded to 64 bytes; the target net is a second
 flat buffer. state_dict(), grads() and checkpoint() convert to the reference's
 names and layouts with torch ops, off the hot path.
+
+Acting with the weights in training goes through actor(): a bf16 DQNForward
+whose buffers snake_dqn_pack32 (dqn_pack_kernels.hip) refills from the master
+weights after every step, one launch, no host sync.
 """
 import ctypes
+import weakref
 
 from ._device import get_torch as _torch, ptr, stream_ptr
 from ._native import ADAM_SCRATCH_BYTES, Dqn32Net, DqnCfg, check, lib
-from .dqn import _check_shapes
+from .dqn import DQNForward, _check_shapes, bf16_plan
 
 # snake_dqn32_net's field order, with the reference's parameter names
 FIELDS = ('conv1_w', 'conv2_w', 'conv3_w', 'fc1_w', 'fc2_w', 'fc3_w',
@@ -66,18 +71,37 @@ class DQNLearner:
     gradient step and returns the loss as a float32 () tensor on the device.
     The stages of update() are methods of their own: td_loss, backward (for
     the observations of the last policy forward), apply; grads() and grad_norm
-    show what they left."""
+    show what they left.
+
+    actor() is a bf16 DQNForward that follows the policy net, for collecting
+    with the policy in training. target_precision='bf16' keeps a second,
+    bf16-packed copy of the target net (refreshed by sync_target(),
+    load_checkpoint() and here) and runs target_q -- so update()'s target
+    forward -- on the bf16 matrix cores with it (plan 'auto'); the fp32 target
+    buffer, target_state_dict() and checkpoint() are the same in both modes,
+    and the default 'fp32' computes exactly what it did without the option.
+    Both need a geometry a bf16 plan accepts (A <= 4, 8 to 32 channels, (h+2) *
+    (w+2) <= 576) and raise ValueError with the plan's message, before any
+    device work, where none does. The bf16 forward reads the observations as
+    0/1 bytes: unlike the fp32 forward it does not take the reference's /255
+    branch."""
 
     def __init__(self, state, height, width, channels, num_actions=3, lr=5e-4, gamma=0.99, betas=(0.9, 0.999),
-                 eps=1e-8, max_grad_norm=10.0, device=None, lib_path=None):
+                 eps=1e-8, max_grad_norm=10.0, device=None, lib_path=None, target_precision='fp32'):
         torch = _torch()
         if hasattr(state, 'state_dict'):
             state = state.state_dict()
         H, W, C, A = int(height), int(width), int(channels), int(num_actions)
         self._L = L = lib(lib_path)
+        self._lib_path = lib_path
         self.cfg = DqnCfg(H, W, C, A, 0)
         n = L.snake_dqn32_train_scratch(ctypes.byref(self.cfg), 0)      # ValueError before any device work
         check(int(n) if n < 0 else 0, L)
+        if target_precision not in ('fp32', 'bf16'):
+            raise ValueError("target_precision must be 'fp32' or 'bf16'")
+        if target_precision == 'bf16':
+            bf16_plan(L, self.cfg)
+        self.target_precision = target_precision
         _check_shapes(state, C, H * W, A)
         if not (lr > 0.0 and eps >= 0.0 and max_grad_norm > 0.0 and 0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError('lr and max_grad_norm must be positive, eps >= 0, betas in [0, 1)')
@@ -112,6 +136,9 @@ class DQNLearner:
         self._scratch = {}          # 'policy' / 'target' / 'train' -> uint8 buffers
         self._fwd = None            # (obs, B) of the last policy forward
         self._keep = None
+        self._actors = weakref.WeakSet()        # the auto_sync actors, held weakly
+        self._target16 = DQNForward.empty(H, W, C, A, device=dev, lib_path=lib_path) \
+            if target_precision == 'bf16' else None
         self._load(self._param, state)
         self.sync_target()
 
@@ -179,7 +206,11 @@ class DQNLearner:
         return self._forward(self._net, 'policy', obs, True, 'forward_features')[1]
 
     def target_q(self, obs):
-        """The target net's Q-values."""
+        """The target net's Q-values (with target_precision='bf16': the bf16
+        forward on the packed copy of the target net)."""
+        if self._target16 is not None:
+            self._check_obs(obs, 'target_q')
+            return self._target16(obs)
         return self._forward(self._tnet, 'target', obs, False, 'target_q')[0]
 
     # ------------------------------------------------------------------ stages
@@ -243,7 +274,8 @@ class DQNLearner:
 
     def apply(self):
         """clip_grad_norm_ and one Adam step from the gradient buffer; the norm
-        before clipping goes to self.grad_norm."""
+        before clipping goes to self.grad_norm. The auto_sync actors are
+        repacked from the new weights."""
         torch = _torch()
         self.step += 1
         with torch.cuda.device(self.device):
@@ -251,6 +283,7 @@ class DQNLearner:
                                           self.step, self.lr, self.betas[0], self.betas[1], self.eps,
                                           self.max_grad_norm, ptr(self._adam_scratch), ptr(self.grad_norm),
                                           stream_ptr(self.device)), self._L)
+        self._sync_actors()
 
     def update(self, state, action, reward, next_state, done):
         """update_model on ReplayBuffer.sample(format='uint8')'s five tensors;
@@ -266,6 +299,42 @@ class DQNLearner:
     def sync_target(self):
         """target_net.load_state_dict(policy_net.state_dict())."""
         self._target.copy_(self._param)
+        if self._target16 is not None:
+            self._target16.pack32(self._tnet)
+
+    # ------------------------------------------------------------------ actors
+    def actor(self, plan='auto', conv_waves=0, auto_sync=True):
+        """A bf16 DQNForward (DQNForward.empty: plan and conv_waves as there)
+        packed from the policy net on the device, for acting with the policy
+        that is being trained: Collector.run(learner.actor(), ...).
+
+        With auto_sync the learner repacks it at the end of every apply() (so
+        of every update()) and load_checkpoint(): one launch on the current
+        stream, no host sync. Without, it keeps its snapshot until actor.sync()
+        (= learner.sync_actor(actor)). The learner holds its auto_sync actors
+        weakly: one that is no longer referenced anywhere else is dropped and
+        costs nothing. A repack is ordered like any other launch on the current
+        stream: act on the stream the updates run on, or order the two streams
+        yourself. Raises ValueError with the plan's message, before any
+        device work, where the plan rejects the geometry. The bf16 forward does
+        not take the /255 branch: it is for the env's 0/1 observations."""
+        a = DQNForward.empty(*self.obs_shape, num_actions=self.num_actions, device=self.device, plan=plan,
+                             conv_waves=conv_waves, lib_path=self._lib_path)
+        a._source = self
+        a.pack32(self._net)
+        if auto_sync:
+            self._actors.add(a)
+        return a
+
+    def sync_actor(self, actor):
+        """Repack an actor of this learner from the policy net, on the current stream."""
+        if getattr(actor, '_source', None) is not self:
+            raise ValueError('sync_actor takes a DQNForward made by this learner\'s actor()')
+        actor.pack32(self._net)
+
+    def _sync_actors(self):
+        for a in list(self._actors):
+            a.pack32(self._net)
 
     def state_dict(self):
         """The policy net with the reference's names and layouts (copies)."""
@@ -294,3 +363,6 @@ class DQNLearner:
         self._load(self._v, opt['exp_avg_sq'])
         self.step = int(opt['step'])
         self._fwd = None
+        if self._target16 is not None:
+            self._target16.pack32(self._tnet)
+        self._sync_actors()
