@@ -400,6 +400,32 @@ int snake_dqn32_backward(const snake_dqn_cfg *cfg, const snake_dqn32_net *net, c
                          int64_t batch, const void *fwd_scratch, const float *dq, void *train_scratch,
                          const snake_dqn32_net *grad, void *stream);
 
+/* snake_dqn32_backward in bf16 mixed precision (dqn_train16_kernels.hip): the
+ * same arguments, preconditions, return codes, scratch layout and split-M rule,
+ * the same operand sources (the fp32 forward's scratch, the uint8 observation,
+ * the fp32 weights, the fp32 dY buffers of train_scratch). The five weight
+ * gradients and four input gradients of the matrix cores run on
+ * v_mfma_f32_16x16x32_bf16: every element of a GEMM operand is rounded to bf16
+ * when it is staged, products are exact and sums are fp32. bf16(v) is round to
+ * nearest even on v's bit pattern (torch's .to(bfloat16)); a NaN keeps its sign
+ * and top mantissa bits and gets the quiet bit. Exactly these are rounded:
+ *   weight gradient  dW[n][k] = sum_m bf16(dY[m][n]) * bf16(act(X)[m][k]),
+ *                    act(X) formed in fp32 first: relu(Y + b), or the byte, or
+ *                    byte / 255 when the flag is set
+ *   input gradient   dX[m][k] = (sum_r bf16(dY[..][r]) * bf16(W[r][k])) * mask
+ * and these are not:
+ *   the mask Y + bias > 0 (fp32, as above);
+ *   dX as it is stored: the fp32 sum, unrounded (dY1..dY4 in train_scratch hold
+ *   fp32 values; the next GEMM rounds them when it stages them);
+ *   the bias gradients: db[n] = sum_m dY[m][n] over the unrounded fp32 dY, in a
+ *   fixed order that depends on the shape alone;
+ *   fc3 (weight, bias and input gradient, so dY5) and the sums of the split-M
+ *   partials: the fp32 function's kernels, bit-equal to it.
+ * No floating-point atomics; results are bitwise reproducible. */
+int snake_dqn32_backward_bf16(const snake_dqn_cfg *cfg, const snake_dqn32_net *net, const uint8_t *obs,
+                              int64_t batch, const void *fwd_scratch, const float *dq, void *train_scratch,
+                              const snake_dqn32_net *grad, void *stream);
+
 /* The TD loss (:243-250), one launch. Per row b, in fp32 and in this order:
  *   target = reward[b] + ((1 - done[b]) * gamma) * max_a next_q[b][a]
  *   d      = q[b][action[b]] - target

@@ -31,6 +31,10 @@
 // partial result, and k_reduce sums the partials in chunk order. With one
 // chunk the result goes straight to the gradient. No floating-point atomics:
 // every sum has a fixed order, results are bitwise reproducible.
+//
+// snake_dqn32_backward_bf16 is the same launch sequence with k_wgrad and k_dgrad
+// replaced by their bf16 forms (dqn_train16_kernels.hip); what the two files
+// share is in dqn_train_shared.h.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -38,7 +42,7 @@
 
 #include <algorithm>
 
-#include "dqn32_shared.h"
+#include "dqn_train_shared.h"
 
 namespace snake {
 namespace train {
@@ -49,20 +53,8 @@ using dqn32::kDense;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kT = 64;          // output tile: kT rows x kT columns
 constexpr int kKT = 16;         // reduction steps per LDS stage
 constexpr int kS = 68;          // LDS row stride in floats: 4 * 68 = 16 mod 64 banks
-constexpr int64_t kChunk = 2048;
-constexpr int64_t kMaxChunks = 128;
-
-__host__ __device__ inline int64_t chunk_rows(int64_t M)
-{
-    int64_t c = (M + kMaxChunks - 1) / kMaxChunks;
-    c = (c + 15) / 16 * 16;
-    return c > kChunk ? c : kChunk;
-}
-inline int64_t num_chunks(int64_t M) { return M < 1 ? 1 : (M + chunk_rows(M) - 1) / chunk_rows(M); }
-
 // 16 reduction steps of the workgroup's LDS tiles into this wave's 2 x 2 tiles
 __device__ inline void mma16(const float *As, const float *Bs, int wr, int wc, int grp, int l16, f32x4 (&acc)[2][2])
 {
@@ -83,20 +75,7 @@ __device__ inline void mma16(const float *As, const float *Bs, int wr, int wc, i
     }
 }
 
-// ---- weight gradient: out[chunk][n][k] = sum_{m in chunk} dY[m][n] * act(X)[m][k]
-struct WgradArgs {
-    const float *dy;        // [M][N], N % 4 == 0
-    const void *x;          // the forward's A source (mode)
-    const float *xbias;     // its bias (modes 1, 2)
-    int bmod;               // bias period along k (mode 2)
-    const int *scale_flag;  // mode 0: nonzero -> uint8 / 255
-    int N, K;               // K % 4 == 0
-    int H, W, C;            // conv geometry (modes 0, 1)
-    int64_t M, chunk;
-    float *out;             // [chunks][N][K]
-    float *bout;            // [chunks][N]: the bias gradient's partials, the column sums of dY
-};
-
+// ---- weight gradient (WgradArgs): out[chunk][n][k] = sum_{m in chunk} dY[m][n] * act(X)[m][k]
 template <int MODE>
 __global__ void __launch_bounds__(256) k_wgrad(const WgradArgs g)
 {
@@ -215,22 +194,7 @@ __global__ void __launch_bounds__(256) k_wgrad(const WgradArgs g)
         }
 }
 
-// ---- input gradient: out[m][k] = (sum_r A(m, r) * B(r, k)) * (yprev[m][k] + pbias > 0)
-//   dense: r = n;         A = dY[m][n],                     B = W[n][k]
-//   conv:  r = (tap, co); A = dY[(b, y+1-dy, x+1-dx)][co],  B = W[co][tap*K + k]   (K = Cin)
-struct DgradArgs {
-    const float *dy;
-    const float *w;
-    const float *yprev;     // [M][K] pre-activations of the layer below
-    const float *pbias;     // their bias, period bmod along k
-    int bmod;
-    float *out;             // [M][K]
-    int64_t M;
-    int R;                  // reduction length (dense: N; conv: 9 * Cout), R % 4 == 0
-    int K;                  // K % 4 == 0
-    int H, W, Cout;         // conv
-};
-
+// ---- input gradient (DgradArgs): out[m][k] = (sum_r A(m, r) * B(r, k)) * (yprev[m][k] + pbias > 0)
 template <bool CONV>
 __global__ void __launch_bounds__(256) k_dgrad(const DgradArgs g)
 {
@@ -493,12 +457,7 @@ __global__ void __launch_bounds__(256) k_adam(float *p, const float *g, float *m
 }
 
 // ---- host side
-// train scratch (floats): dY5 [B][128] | dY4 [B][256] | dY3 [BP][64] | dY2 [BP][64]
-// | dY1 [BP][32] | weight partials | bias partials
-struct TrainScratch {
-    float *dy5, *dy4, *dy3, *dy2, *dy1, *wpart, *bpart;
-};
-
+// (the train scratch: TrainScratch in dqn_train_shared.h)
 int64_t train_scratch_bytes(const snake_dqn_cfg *cfg, int64_t B, void *base, TrainScratch *out)
 {
     const int64_t P = (int64_t)cfg->height * cfg->width, BP = B * P;
@@ -602,14 +561,17 @@ extern "C" int64_t snake_dqn32_train_scratch(const snake_dqn_cfg *cfg, int64_t b
     return train::train_scratch_bytes(cfg, batch, nullptr, nullptr);
 }
 
-extern "C" int snake_dqn32_backward(const snake_dqn_cfg *cfg, const snake_dqn32_net *net, const uint8_t *obs,
-                                    int64_t batch, const void *fwd_scratch, const float *dq, void *train_scratch,
-                                    const snake_dqn32_net *grad_net, void *stream)
+// The backward of both precisions: one validation and one launch sequence. With
+// bf16 the five weight gradients and four input gradients of the matrix cores
+// go to dqn_train16_kernels.hip's kernels; fc3 and the reductions are the same.
+static int backward(const char *who, bool bf16, const snake_dqn_cfg *cfg, const snake_dqn32_net *net,
+                    const uint8_t *obs, int64_t batch, const void *fwd_scratch, const float *dq, void *train_scratch,
+                    const snake_dqn32_net *grad_net, void *stream)
 {
-    int rc = train::check_train(cfg, batch, "snake_dqn32_backward");
+    int rc = train::check_train(cfg, batch, who);
     if (rc) return rc;
     if (!net || !obs || !fwd_scratch || !dq || !train_scratch || !grad_net) {
-        set_error("snake_dqn32_backward: NULL buffer");
+        set_error("%s: NULL buffer", who);
         return SNAKE_E_ARG;
     }
     // the gradient block: snake_dqn32_net's twelve pointers, written here
@@ -623,14 +585,14 @@ extern "C" int snake_dqn32_backward(const snake_dqn_cfg *cfg, const snake_dqn32_
     float *const grads[12] = {grad->conv1_w, grad->conv2_w, grad->conv3_w, grad->fc1_w, grad->fc2_w, grad->fc3_w,
                               grad->conv1_b, grad->conv2_b, grad->conv3_b, grad->fc1_b, grad->fc2_b, grad->fc3_b};
     for (int i = 0; i < 12; i++) {
-        if (!wts[i] || !grads[i]) { set_error("snake_dqn32_backward: NULL weight or gradient pointer"); return SNAKE_E_ARG; }
+        if (!wts[i] || !grads[i]) { set_error("%s: NULL weight or gradient pointer", who); return SNAKE_E_ARG; }
         if (((uintptr_t)wts[i] | (uintptr_t)grads[i]) & 15) {
-            set_error("snake_dqn32_backward: weights and gradients must be 16-byte aligned");
+            set_error("%s: weights and gradients must be 16-byte aligned", who);
             return SNAKE_E_ARG;
         }
     }
     if (((uintptr_t)fwd_scratch | (uintptr_t)train_scratch) & 15) {
-        set_error("snake_dqn32_backward: the scratch buffers must be 16-byte aligned");
+        set_error("%s: the scratch buffers must be 16-byte aligned", who);
         return SNAKE_E_ARG;
     }
     if (batch == 0) return SNAKE_OK;
@@ -655,6 +617,17 @@ extern "C" int snake_dqn32_backward(const snake_dqn_cfg *cfg, const snake_dqn32_
                            net->fc3_w, fw.y5, net->fc2_b, batch, A, ts.dy5);
         if ((rc = train::launched("fc3 input gradient"))) return rc;
     }
+    auto wgrad = [&](int mode, const train::WgradArgs &g, float *gw, float *gb, const train::TrainScratch &t,
+                     hipStream_t st, const char *what) {
+        if (bf16) return train::wgrad16(mode, g, gw, gb, t, st, what);
+        if (mode == dqn32::kDense) return train::wgrad<dqn32::kDense>(g, gw, gb, t, st, what);
+        if (mode == dqn32::kConvF32) return train::wgrad<dqn32::kConvF32>(g, gw, gb, t, st, what);
+        return train::wgrad<dqn32::kConvU8>(g, gw, gb, t, st, what);
+    };
+    auto dgrad = [&](bool conv, const train::DgradArgs &g, hipStream_t st, const char *what) {
+        if (bf16) return train::dgrad16(conv, g, st, what);
+        return conv ? train::dgrad<true>(g, st, what) : train::dgrad<false>(g, st, what);
+    };
     train::WgradArgs wg{};
     train::DgradArgs dg{};
     wg.H = dg.H = H;
@@ -662,31 +635,47 @@ extern "C" int snake_dqn32_backward(const snake_dqn_cfg *cfg, const snake_dqn32_
     wg.scale_flag = fw.flag;
     // ---- fc2: dY5 [B][128], A = relu(Y4 + bfc1) [B][256]
     wg.dy = ts.dy5; wg.N = 128; wg.x = fw.y4; wg.xbias = net->fc1_b; wg.bmod = 256; wg.K = 256; wg.M = batch;
-    if ((rc = train::wgrad<dqn32::kDense>(wg, grad->fc2_w, grad->fc2_b, ts, s, "fc2 weight and bias gradient"))) return rc;
+    if ((rc = wgrad(dqn32::kDense, wg, grad->fc2_w, grad->fc2_b, ts, s, "fc2 weight and bias gradient"))) return rc;
     dg.dy = ts.dy5; dg.w = net->fc2_w; dg.yprev = fw.y4; dg.pbias = net->fc1_b; dg.bmod = 256; dg.out = ts.dy4;
     dg.M = batch; dg.R = 128; dg.K = 256;
-    if ((rc = train::dgrad<false>(dg, s, "fc2 input gradient"))) return rc;
+    if ((rc = dgrad(false, dg, s, "fc2 input gradient"))) return rc;
     // ---- fc1: dY4 [B][256], A = relu(Y3 + b3) flattened NHWC [B][64 P]
     wg.dy = ts.dy4; wg.N = 256; wg.x = fw.y3; wg.xbias = net->conv3_b; wg.bmod = 64; wg.K = (int)(64 * P);
-    if ((rc = train::wgrad<dqn32::kDense>(wg, grad->fc1_w, grad->fc1_b, ts, s, "fc1 weight and bias gradient"))) return rc;
+    if ((rc = wgrad(dqn32::kDense, wg, grad->fc1_w, grad->fc1_b, ts, s, "fc1 weight and bias gradient"))) return rc;
     dg.dy = ts.dy4; dg.w = net->fc1_w; dg.yprev = fw.y3; dg.pbias = net->conv3_b; dg.bmod = 64; dg.out = ts.dy3;
     dg.R = 256; dg.K = (int)(64 * P);
-    if ((rc = train::dgrad<false>(dg, s, "fc1 input gradient"))) return rc;
+    if ((rc = dgrad(false, dg, s, "fc1 input gradient"))) return rc;
     // ---- conv3: dY3 [BP][64], A = relu(Y2 + b2) patches
     wg.dy = ts.dy3; wg.N = 64; wg.x = fw.y2; wg.xbias = net->conv2_b; wg.C = 64; wg.K = 576; wg.M = BP;
-    if ((rc = train::wgrad<dqn32::kConvF32>(wg, grad->conv3_w, grad->conv3_b, ts, s, "conv3 weight and bias gradient"))) return rc;
+    if ((rc = wgrad(dqn32::kConvF32, wg, grad->conv3_w, grad->conv3_b, ts, s, "conv3 weight and bias gradient"))) return rc;
     dg.dy = ts.dy3; dg.w = net->conv3_w; dg.yprev = fw.y2; dg.pbias = net->conv2_b; dg.bmod = 64; dg.out = ts.dy2;
     dg.M = BP; dg.R = 576; dg.K = 64; dg.Cout = 64;
-    if ((rc = train::dgrad<true>(dg, s, "conv3 input gradient"))) return rc;
+    if ((rc = dgrad(true, dg, s, "conv3 input gradient"))) return rc;
     // ---- conv2: dY2 [BP][64], A = relu(Y1 + b1) patches
     wg.dy = ts.dy2; wg.x = fw.y1; wg.xbias = net->conv1_b; wg.C = 32; wg.K = 288;
-    if ((rc = train::wgrad<dqn32::kConvF32>(wg, grad->conv2_w, grad->conv2_b, ts, s, "conv2 weight and bias gradient"))) return rc;
+    if ((rc = wgrad(dqn32::kConvF32, wg, grad->conv2_w, grad->conv2_b, ts, s, "conv2 weight and bias gradient"))) return rc;
     dg.dy = ts.dy2; dg.w = net->conv2_w; dg.yprev = fw.y1; dg.pbias = net->conv1_b; dg.bmod = 32; dg.out = ts.dy1;
     dg.K = 32;
-    if ((rc = train::dgrad<true>(dg, s, "conv2 input gradient"))) return rc;
+    if ((rc = dgrad(true, dg, s, "conv2 input gradient"))) return rc;
     // ---- conv1: dY1 [BP][32], A = the observation as the forward read it
     wg.dy = ts.dy1; wg.N = 32; wg.x = obs; wg.xbias = nullptr; wg.C = C; wg.K = 9 * C;
-    return train::wgrad<dqn32::kConvU8>(wg, grad->conv1_w, grad->conv1_b, ts, s, "conv1 weight and bias gradient");
+    return wgrad(dqn32::kConvU8, wg, grad->conv1_w, grad->conv1_b, ts, s, "conv1 weight and bias gradient");
+}
+
+extern "C" int snake_dqn32_backward(const snake_dqn_cfg *cfg, const snake_dqn32_net *net, const uint8_t *obs,
+                                    int64_t batch, const void *fwd_scratch, const float *dq, void *train_scratch,
+                                    const snake_dqn32_net *grad_net, void *stream)
+{
+    return backward("snake_dqn32_backward", false, cfg, net, obs, batch, fwd_scratch, dq, train_scratch, grad_net,
+                    stream);
+}
+
+extern "C" int snake_dqn32_backward_bf16(const snake_dqn_cfg *cfg, const snake_dqn32_net *net, const uint8_t *obs,
+                                         int64_t batch, const void *fwd_scratch, const float *dq,
+                                         void *train_scratch, const snake_dqn32_net *grad_net, void *stream)
+{
+    return backward("snake_dqn32_backward_bf16", true, cfg, net, obs, batch, fwd_scratch, dq, train_scratch,
+                    grad_net, stream);
 }
 
 extern "C" int snake_dqn_td_loss(const float *q, const int64_t *action, const float *reward, const float *done,

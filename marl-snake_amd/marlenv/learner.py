@@ -6,7 +6,8 @@ backward, clip_grad_norm_(10) and optim.Adam.step(). DQNLearner is that step in
 fp32 on the device: the forward of dqn32_kernels.hip, and the backward pass, TD
 loss and clip + Adam of dqn_train_kernels.hip (snake_dqn32_backward,
 snake_dqn_td_loss, snake_adam_step; the exact semantics are in
-include/snake_env.h). Nothing in update() syncs with the host.
+include/snake_env.h). backward_precision='bf16' swaps the backward's GEMMs for
+their bf16 forms (dqn_train16_kernels.hip, snake_dqn32_backward_bf16). Nothing in update() syncs with the host.
 
 The master weights are the fp32 kernels' own layouts (snake_dqn32_net), so
 acting, the target forward and the update need no repacking: parameters,
@@ -84,10 +85,20 @@ class DQNLearner:
     (w+2) <= 576) and raise ValueError with the plan's message, before any
     device work, where none does. The bf16 forward reads the observations as
     0/1 bytes: unlike the fp32 forward it does not take the reference's /255
-    branch."""
+    branch.
+
+    backward_precision='bf16' runs backward() -- so update()'s -- weight and
+    input gradients on the bf16 matrix cores (snake_dqn32_backward_bf16: the
+    GEMM operands rounded to bf16 as they are staged, fp32 sums; the rounding
+    points are in include/snake_env.h). The forwards, the fp32 master weights,
+    Adam, grads(), state_dict(), checkpoint() and actor() are the same in both
+    modes, a checkpoint of one loads into the other, and the default 'fp32'
+    computes exactly what it did without the option. Any geometry the fp32
+    backward accepts."""
 
     def __init__(self, state, height, width, channels, num_actions=3, lr=5e-4, gamma=0.99, betas=(0.9, 0.999),
-                 eps=1e-8, max_grad_norm=10.0, device=None, lib_path=None, target_precision='fp32'):
+                 eps=1e-8, max_grad_norm=10.0, device=None, lib_path=None, target_precision='fp32',
+                 backward_precision='fp32'):
         torch = _torch()
         if hasattr(state, 'state_dict'):
             state = state.state_dict()
@@ -102,6 +113,9 @@ class DQNLearner:
         if target_precision == 'bf16':
             bf16_plan(L, self.cfg)
         self.target_precision = target_precision
+        if backward_precision not in ('fp32', 'bf16'):
+            raise ValueError("backward_precision must be 'fp32' or 'bf16'")
+        self.backward_precision = backward_precision
         _check_shapes(state, C, H * W, A)
         if not (lr > 0.0 and eps >= 0.0 and max_grad_norm > 0.0 and 0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError('lr and max_grad_norm must be positive, eps >= 0, betas in [0, 1)')
@@ -267,9 +281,10 @@ class DQNLearner:
         check(need if need < 0 else 0, self._L)
         ts = self._buffer('train', need)
         with torch.cuda.device(self.device):
-            check(self._L.snake_dqn32_backward(ctypes.byref(self.cfg), ctypes.byref(self._net), ptr(obs), B,
-                                               ptr(self._scratch['policy']), ptr(dq), ptr(ts),
-                                               ctypes.byref(self._gnet), stream_ptr(self.device)), self._L)
+            fn = self._L.snake_dqn32_backward_bf16 if self.backward_precision == 'bf16' \
+                else self._L.snake_dqn32_backward
+            check(fn(ctypes.byref(self.cfg), ctypes.byref(self._net), ptr(obs), B, ptr(self._scratch['policy']),
+                     ptr(dq), ptr(ts), ctypes.byref(self._gnet), stream_ptr(self.device)), self._L)
         self._keep_dq = dq
 
     def apply(self):

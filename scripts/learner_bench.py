@@ -21,6 +21,13 @@ name and its ordinal among that name's dispatches in the update (the backward
 launches its GEMMs in a fixed order: fc2, fc1, conv3, conv2, conv1), takes the
 median duration per label and adds, for the GEMMs, the algorithmic FLOPs and
 their fraction of the 157.3 TF fp32 matrix peak.
+
+--backward-precision bf16 builds the learner with backward_precision='bf16'
+(also for --trace-loop; --fold-trace knows the bf16 kernels' names and adds
+their fraction of the 2.5 PF bf16 peak). --backward-precision both times
+backward and update of an fp32-mode and a bf16-mode learner in one process on
+the same batches, by the same method, and writes the record to
+profiles/learner_bf16_bench.json (or --out).
 """
 import argparse
 import csv
@@ -33,6 +40,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'marl-snake_amd'))
 
 FP32_MATRIX_PEAK = 157.3e12
+BF16_MATRIX_PEAK = 2.5e15
+BF16_RECORD = os.path.join(ROOT, 'profiles', 'learner_bf16_bench.json')
 SHAPES = {'config_20x20x8': (20, 20, 8), 'vision5_11x11x8': (11, 11, 8)}
 BATCH = 512
 
@@ -87,6 +96,8 @@ def fold_trace(path, updates, shape):
     gemms = {}
     for label, e in out.items():
         base = label.split(' #')[0]
+        is16 = base.startswith('k_wgrad16') or base.startswith('k_dgrad16')
+        base = base.replace('k_wgrad16', 'k_wgrad').replace('k_dgrad16', 'k_dgrad')
         j = int(label.split('#')[1]) if '#' in label else 0
         layer = None
         if base.startswith('k_wgrad<2>') or base.startswith('k_wgrad<(int)2>'):
@@ -103,6 +114,8 @@ def fold_trace(path, updates, shape):
             f = flops[layer]
             gemms[layer] = {'median_us': e['median_us'], 'flops': f,
                             'frac_of_fp32_matrix_peak': f / (e['median_us'] * 1e-6) / FP32_MATRIX_PEAK}
+            if is16:
+                gemms[layer]['frac_of_bf16_matrix_peak'] = f / (e['median_us'] * 1e-6) / BF16_MATRIX_PEAK
     return {'shape': shape, 'updates_traced': updates, 'kernels_us': out, 'backward_gemms': gemms,
             'order_in_backward': order}
 
@@ -119,13 +132,18 @@ def main():
     ap.add_argument('--fold-trace', default=None, help='a rocprofv3 kernel trace CSV of a --trace-loop run')
     ap.add_argument('--updates', type=int, default=30, help='--fold-trace: the updates the trace holds')
     ap.add_argument('--record', default=None, help='--fold-trace: the JSON record to add the kernels to')
+    ap.add_argument('--backward-precision', default='fp32', choices=('fp32', 'bf16', 'both'),
+                    help="the learner's backward_precision; both: backward and update in each mode, side by side")
     args = ap.parse_args()
     if args.fold_trace:
         rec = fold_trace(args.fold_trace, args.updates, args.trace_shape)
         if args.record:
             with open(args.record) as fp:
                 whole = json.load(fp)
-            whole['kernel_trace'] = rec
+            if whole.get('metric') == 'dqn_backward_bf16_us':       # one trace per shape, of the bf16 mode
+                whole.setdefault('kernel_traces', {})[args.trace_shape] = rec
+            else:
+                whole['kernel_trace'] = rec
             with open(args.record, 'w') as fp:
                 fp.write(json.dumps(whole, indent=1) + '\n')
         print(json.dumps(rec))
@@ -188,19 +206,51 @@ def main():
     def spread(v):
         return {'median_us': sorted(v)[len(v) // 2], 'repeats_us': v}
 
-    def setup(shape):
+    def setup(shape, precision=None):
         h, w, c = SHAPES[shape]
         torch.manual_seed(0)
         policy, target = TorchDQN(h, w, c, 3).cuda(), TorchDQN(h, w, c, 3).cuda()
         target.load_state_dict(policy.state_dict())
-        learner = DQNLearner(policy.state_dict(), h, w, c, num_actions=3)
+        learner = DQNLearner(policy.state_dict(), h, w, c, num_actions=3,
+                             backward_precision=precision or args.backward_precision)
         return h, w, c, policy, target, learner, [batch(h, w, c, s) for s in range(4)]
 
     if args.trace_loop:
+        if args.backward_precision == 'both':
+            sys.exit('--trace-loop traces one mode: --backward-precision fp32 or bf16')
         h, w, c, _, _, learner, batches = setup(args.trace_shape)
         for i in range(args.trace_loop):
             learner.update(*batches[i % len(batches)])
         torch.cuda.synchronize()
+        return
+
+    if args.backward_precision == 'both':
+        rec = {'metric': 'dqn_backward_bf16_us', 'device': torch.cuda.get_device_name(0), 'batch': BATCH,
+               'launches': args.launches, 'warmup': args.warmup, 'repeats': args.repeats,
+               'timing': 'one HIP event pair per call, enqueued behind ~30 ms of filler work',
+               'yardstick': "the fp32-mode learner (backward_precision='fp32') timed in the same process on the "
+                            'same batches'}
+        for shape in args.shapes.split(','):
+            e = {}
+            for mode in ('fp32', 'bf16'):
+                h, w, c, _, _, learner, batches = setup(shape, mode)
+                s, a, r, ns, d = batches[0]
+                m = {'update': spread(medians_us(lambda b: learner.update(*b), batches))}
+                nq, q = learner.target_q(ns), learner(s)
+                loss, dq = learner.td_loss(q, a, r, d, nq)
+                m['backward'] = spread(medians_us(lambda b: learner.backward(s, dq), batches))
+                e[mode] = m
+                del learner
+            e['obs_shape'] = [h, w, c]
+            e['backward_gemm_flops'] = sum(gemm_flops(h, w, c).values())
+            for stage in ('backward', 'update'):
+                e['%s_bf16_over_fp32' % stage] = e['bf16'][stage]['median_us'] / e['fp32'][stage]['median_us']
+            rec[shape] = e
+        print(json.dumps(rec), flush=True)
+        out = args.out or BF16_RECORD
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, 'w') as fp:
+            fp.write(json.dumps(rec, indent=1) + '\n')
         return
 
     rec = {'metric': 'dqn_update_us', 'device': torch.cuda.get_device_name(0), 'batch': BATCH,
