@@ -389,9 +389,7 @@ int conv_mfma(const GemmArgs &g, hipStream_t s, const char *what)
     // 9.84 -> 9.75 ms; parity green)
     if constexpr (NT == 4) hipLaunchKernelGGL((k_conv32_mfma<MODE, 4, true>), grid, dim3(256), (size_t)lds, s, g);
     else hipLaunchKernelGGL((k_conv32_mfma<MODE, NT>), grid, dim3(256), (size_t)lds, s, g);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) { set_error("%s launch failed: %s", what, hipGetErrorString(err)); return SNAKE_E_LAUNCH; }
-    return SNAKE_OK;
+    return launched(what);
 }
 
 // The dense layers with N a multiple of 128 (fc1: 64hw -> 256, fc2: 256 -> 128)
@@ -592,9 +590,7 @@ int fc_mfma(const GemmArgs &g, hipStream_t s, const char *what)
         hipLaunchKernelGGL(k_fc32_mfma_small, dim3((unsigned)((g.M + 31) / 32), (unsigned)(g.N / 32)), dim3(256), 0, s, g);
     else
         hipLaunchKernelGGL(k_fc32_mfma, grid, dim3(512), 0, s, g);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) { set_error("%s launch failed: %s", what, hipGetErrorString(err)); return SNAKE_E_LAUNCH; }
-    return SNAKE_OK;
+    return launched(what);
 }
 
 // flag = any observation byte > 1 (the reference's x.max() > 1.0 test)
@@ -621,9 +617,7 @@ int gemm(const GemmArgs &g, hipStream_t s, const char *what)
 {
     const dim3 grid((unsigned)((g.M + BM - 1) / BM), (unsigned)((g.N + BN - 1) / BN));
     hipLaunchKernelGGL(k_gemm32<MODE>, grid, dim3(kThreads), 0, s, g);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) { set_error("%s launch failed: %s", what, hipGetErrorString(err)); return SNAKE_E_LAUNCH; }
-    return SNAKE_OK;
+    return launched(what);
 }
 
 }  // namespace dqn32
@@ -662,7 +656,7 @@ extern "C" int snake_dqn32_forward(const snake_dqn_cfg *cfg, const snake_dqn32_n
         const int64_t n = BP * C;
         const unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, 4096);
         hipLaunchKernelGGL(dqn32::k_obs_max, dim3(blocks), dim3(256), 0, s, obs, n, sc.flag);
-        if (hipGetLastError() != hipSuccess) { set_error("k_obs_max launch failed"); return SNAKE_E_LAUNCH; }
+        if ((rc = launched("k_obs_max"))) return rc;
     }
     dqn32::GemmArgs g{};
     g.H = H; g.W = W;
@@ -700,7 +694,7 @@ extern "C" int snake_dqn32_forward(const snake_dqn_cfg *cfg, const snake_dqn32_n
         const int64_t total = batch * 128;
         hipLaunchKernelGGL(dqn32::k_bias_relu, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, sc.y5,
                            net->fc2_b, 128, total, feat_out);
-        if (hipGetLastError() != hipSuccess) { set_error("k_bias_relu launch failed"); return SNAKE_E_LAUNCH; }
+        if ((rc = launched("k_bias_relu"))) return rc;
     }
     return SNAKE_OK;
 }

@@ -807,6 +807,47 @@ int g_conv_grid[3][5][3];
 // (two for odd row-tile counts). Forward at 262144 observations: 4.51 / 4.57 /
 // 5.91 ms for 4 / 2 / 1 (conv_waves selects the others).
 int conv_waves() { return 4; }
+
+// ---- what snake_dqn_forward and snake_dqn_map_forward share --------------
+int check_forward(const char *who, const snake_dqn_net *net, const uint8_t *obs, int64_t batch,
+                  const uint16_t *act_scratch, const float *q_out)
+{
+    if (!net || !obs || !act_scratch || !q_out || !net->conv1_w || !net->conv2_w || !net->conv3_w ||
+        !net->fc1_w || !net->fc2_w || !net->conv1_b || !net->conv2_b || !net->conv3_b || !net->fc1_b ||
+        !net->fc2_b || !net->fc3_w || !net->fc3_b) {
+        set_error("%s: NULL buffer", who);
+        return SNAKE_E_ARG;
+    }
+    if (batch < 0) { set_error("%s: batch < 0", who); return SNAKE_E_ARG; }
+    return SNAKE_OK;
+}
+
+// persistent grid: the resident workgroups of the whole device (0, and the error set, where the query fails)
+int persistent_grid(const char *who, const void *kernel, int threads, int lds)
+{
+    int per_cu = 0, dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds) != hipSuccess ||
+        per_cu < 1 || cus < 1) {
+        set_error("%s: occupancy query failed", who);
+        return 0;
+    }
+    return per_cu * cus;
+}
+
+// the fc layers on the conv kernel's output (either plan's)
+int launch_fc(const snake_dqn_cfg *cfg, const snake_dqn_layout &lay, const snake_dqn_net *net, int64_t batch,
+              const uint16_t *act_scratch, float *q_out, float *feat_out, hipStream_t s)
+{
+    FcArgs fa;
+    fa.act = act_scratch; fa.B = batch; fa.K = (int)lay.act_per_obs; fa.A = cfg->num_actions;
+    fa.w4 = net->fc1_w; fa.b4 = net->fc1_b; fa.w5 = net->fc2_w; fa.b5 = net->fc2_b;
+    fa.w6 = net->fc3_w; fa.b6 = net->fc3_b; fa.q = q_out; fa.feat = feat_out;
+    const unsigned gfc = (unsigned)((batch + kFcObs - 1) / kFcObs);
+    hipLaunchKernelGGL(k_dqn_fc, dim3(gfc), dim3(512), 0, s, fa);
+    return launched("k_dqn_fc");
+}
 }  // namespace
 
 extern "C" int snake_dqn_plan(const snake_dqn_cfg *cfg, snake_dqn_layout *out)
@@ -865,13 +906,7 @@ extern "C" int snake_dqn_forward(const snake_dqn_cfg *cfg, const snake_dqn_net *
     snake_dqn_layout lay;
     int rc = snake_dqn_plan(cfg, &lay);
     if (rc) return rc;
-    if (!net || !obs || !act_scratch || !q_out || !net->conv1_w || !net->conv2_w || !net->conv3_w ||
-        !net->fc1_w || !net->fc2_w || !net->conv1_b || !net->conv2_b || !net->conv3_b || !net->fc1_b ||
-        !net->fc2_b || !net->fc3_w || !net->fc3_b) {
-        set_error("snake_dqn_forward: NULL buffer");
-        return SNAKE_E_ARG;
-    }
-    if (batch < 0) { set_error("snake_dqn_forward: batch < 0"); return SNAKE_E_ARG; }
+    if ((rc = check_forward("snake_dqn_forward", net, obs, batch, act_scratch, q_out))) return rc;
     if (batch == 0) return SNAKE_OK;
     const hipStream_t s = (hipStream_t)stream;
     ConvArgs ca;
@@ -885,30 +920,11 @@ extern "C" int snake_dqn_forward(const snake_dqn_cfg *cfg, const snake_dqn_net *
     const conv_kernel_t kc = ck.k;
     const int nw = ck.nw;
     int &grid = g_conv_grid[want == 1 ? 0 : (want == 2 ? 1 : 2)][vi][ci];
-    if (!grid) {   // persistent grid: the resident workgroups of the whole device
-        int per_cu = 0, dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kc, 64 * nw, 0) != hipSuccess ||
-            per_cu < 1 || cus < 1) {
-            set_error("snake_dqn_forward: occupancy query failed");
-            return SNAKE_E_LAUNCH;
-        }
-        grid = per_cu * cus;
-    }
+    if (!grid && !(grid = persistent_grid("snake_dqn_forward", (const void *)kc, 64 * nw, 0))) return SNAKE_E_LAUNCH;
     const unsigned gconv = (unsigned)std::min<int64_t>(batch, grid);
     hipLaunchKernelGGL(kc, dim3(gconv), dim3(64 * nw), 0, s, ca);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) { set_error("k_dqn_conv launch failed: %s", hipGetErrorString(err)); return SNAKE_E_LAUNCH; }
-    FcArgs fa;
-    fa.act = act_scratch; fa.B = batch; fa.K = (int)lay.act_per_obs; fa.A = cfg->num_actions;
-    fa.w4 = net->fc1_w; fa.b4 = net->fc1_b; fa.w5 = net->fc2_w; fa.b5 = net->fc2_b;
-    fa.w6 = net->fc3_w; fa.b6 = net->fc3_b; fa.q = q_out; fa.feat = feat_out;
-    const unsigned gfc = (unsigned)((batch + kFcObs - 1) / kFcObs);
-    hipLaunchKernelGGL(k_dqn_fc, dim3(gfc), dim3(512), 0, s, fa);
-    err = hipGetLastError();
-    if (err != hipSuccess) { set_error("k_dqn_fc launch failed: %s", hipGetErrorString(err)); return SNAKE_E_LAUNCH; }
-    return SNAKE_OK;
+    if ((rc = launched("k_dqn_conv"))) return rc;
+    return launch_fc(cfg, lay, net, batch, act_scratch, q_out, feat_out, s);
 }
 
 // ---- the map path's host side --------------------------------------------
@@ -1006,13 +1022,7 @@ extern "C" int snake_dqn_map_forward(const snake_dqn_cfg *cfg, const snake_dqn_n
     snake_dqn_layout lay;
     int rc = snake_dqn_map_plan(cfg, &lay);
     if (rc) return rc;
-    if (!net || !obs || !act_scratch || !q_out || !net->conv1_w || !net->conv2_w || !net->conv3_w ||
-        !net->fc1_w || !net->fc2_w || !net->conv1_b || !net->conv2_b || !net->conv3_b || !net->fc1_b ||
-        !net->fc2_b || !net->fc3_w || !net->fc3_b) {
-        set_error("snake_dqn_map_forward: NULL buffer");
-        return SNAKE_E_ARG;
-    }
-    if (batch < 0) { set_error("snake_dqn_map_forward: batch < 0"); return SNAKE_E_ARG; }
+    if ((rc = check_forward("snake_dqn_map_forward", net, obs, batch, act_scratch, q_out))) return rc;
     if (batch == 0) return SNAKE_OK;
     const hipStream_t s = (hipStream_t)stream;
     MapArgs ma;
@@ -1037,29 +1047,14 @@ extern "C" int snake_dqn_map_forward(const snake_dqn_cfg *cfg, const snake_dqn_n
         }
         mk.big_lds = true;
     }
-    if (mk.lds != lay.lds_conv) {   // persistent grid: the resident workgroups of the whole device
-        int per_cu = 0, dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)mk.k, 64 * nw, lay.lds_conv) != hipSuccess ||
-            per_cu < 1 || cus < 1) {
-            set_error("snake_dqn_map_forward: occupancy query failed");
-            return SNAKE_E_LAUNCH;
-        }
-        mk.grid = per_cu * cus;
+    if (mk.lds != lay.lds_conv) {   // the grid depends on the LDS a workgroup takes
+        const int grid = persistent_grid("snake_dqn_map_forward", (const void *)mk.k, 64 * nw, lay.lds_conv);
+        if (!grid) return SNAKE_E_LAUNCH;
+        mk.grid = grid;
         mk.lds = lay.lds_conv;
     }
     const unsigned gconv = (unsigned)std::min<int64_t>(batch, mk.grid);
     hipLaunchKernelGGL(mk.k, dim3(gconv), dim3(64 * nw), lay.lds_conv, s, ma);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) { set_error("k_dqn_map_conv launch failed: %s", hipGetErrorString(err)); return SNAKE_E_LAUNCH; }
-    FcArgs fa;
-    fa.act = act_scratch; fa.B = batch; fa.K = (int)lay.act_per_obs; fa.A = cfg->num_actions;
-    fa.w4 = net->fc1_w; fa.b4 = net->fc1_b; fa.w5 = net->fc2_w; fa.b5 = net->fc2_b;
-    fa.w6 = net->fc3_w; fa.b6 = net->fc3_b; fa.q = q_out; fa.feat = feat_out;
-    const unsigned gfc = (unsigned)((batch + kFcObs - 1) / kFcObs);
-    hipLaunchKernelGGL(k_dqn_fc, dim3(gfc), dim3(512), 0, s, fa);
-    err = hipGetLastError();
-    if (err != hipSuccess) { set_error("k_dqn_fc launch failed: %s", hipGetErrorString(err)); return SNAKE_E_LAUNCH; }
-    return SNAKE_OK;
+    if ((rc = launched("k_dqn_map_conv"))) return rc;
+    return launch_fc(cfg, lay, net, batch, act_scratch, q_out, feat_out, s);
 }

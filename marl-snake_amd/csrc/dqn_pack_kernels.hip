@@ -254,9 +254,7 @@ extern "C" int snake_dqn_pack32(const snake_dqn_cfg *cfg, int32_t map_plan, cons
     for (int i = 0; i < kCopies; i++) small += a.cnum[i];
     const unsigned grid = (unsigned)(a.fc1_blocks + (small + 255) / 256);
     hipLaunchKernelGGL(k_dqn_pack, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) { set_error("k_dqn_pack launch failed: %s", hipGetErrorString(err)); return SNAKE_E_LAUNCH; }
-    return SNAKE_OK;
+    return launched("k_dqn_pack");
 }
 
 extern "C" int snake_dqn_pack32_host(const snake_dqn_cfg *cfg, int32_t map_plan, const snake_dqn32_net *src,

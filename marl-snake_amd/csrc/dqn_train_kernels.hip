@@ -488,13 +488,6 @@ int64_t train_scratch_bytes(const snake_dqn_cfg *cfg, int64_t B, void *base, Tra
     return 4 * (n5 + n4 + n3 + n2 + n1 + wp + bp);
 }
 
-int launched(const char *what)
-{
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) { set_error("%s launch failed: %s", what, hipGetErrorString(err)); return SNAKE_E_LAUNCH; }
-    return SNAKE_OK;
-}
-
 int reduce(const float *wpart, const float *bpart, int64_t chunks, int64_t nw, int64_t nb, float *wout, float *bout,
            hipStream_t s, const char *what)
 {
@@ -608,14 +601,14 @@ static int backward(const char *who, bool bf16, const snake_dqn_cfg *cfg, const 
         const int64_t chunks = train::num_chunks(batch);
         hipLaunchKernelGGL(train::k_fc3_wgrad, dim3((unsigned)chunks, (unsigned)A), dim3(1024), 0, s, dq, fw.y5,
                            net->fc2_b, batch, A, train::chunk_rows(batch), chunks > 1 ? ts.wpart : grad->fc3_w);
-        if ((rc = train::launched("fc3 weight gradient"))) return rc;
+        if ((rc = launched("fc3 weight gradient"))) return rc;
         if (chunks > 1 && (rc = train::reduce(ts.wpart, ts.wpart, chunks, (int64_t)A * 128, 0, grad->fc3_w,
                                               grad->fc3_w, s, "fc3 weight gradient")))
             return rc;
         if ((rc = train::colsum(dq, batch, A, grad->fc3_b, ts.bpart, s, "fc3 bias gradient"))) return rc;
         hipLaunchKernelGGL(train::k_fc3_dgrad, dim3((unsigned)((batch * 128 + 255) / 256)), dim3(256), 0, s, dq,
                            net->fc3_w, fw.y5, net->fc2_b, batch, A, ts.dy5);
-        if ((rc = train::launched("fc3 input gradient"))) return rc;
+        if ((rc = launched("fc3 input gradient"))) return rc;
     }
     auto wgrad = [&](int mode, const train::WgradArgs &g, float *gw, float *gb, const train::TrainScratch &t,
                      hipStream_t st, const char *what) {
@@ -696,7 +689,7 @@ extern "C" int snake_dqn_td_loss(const float *q, const int64_t *action, const fl
     }
     hipLaunchKernelGGL(train::k_td_loss, dim3(1), dim3(256), 0, (hipStream_t)stream, q, action, reward, done, next_q,
                        batch, num_actions, gamma, loss_out, dq, err);
-    return train::launched("k_td_loss");
+    return launched("k_td_loss");
 }
 
 extern "C" int snake_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
@@ -719,14 +712,14 @@ extern "C" int snake_adam_step(float *param, const float *grad, float *exp_avg, 
     const int G = (int)std::min<int64_t>(train::kNormBlocks, (n + 1023) / 1024);
     const int64_t L = ((n + G - 1) / G + 255) / 256 * 256;
     hipLaunchKernelGGL(train::k_sumsq, dim3(G), dim3(256), 0, s, grad, n, L, sc);
-    int rc = train::launched("k_sumsq");
+    int rc = launched("k_sumsq");
     if (rc) return rc;
     hipLaunchKernelGGL(train::k_norm, dim3(1), dim3(256), 0, s, sc, G, norm_out);
-    if ((rc = train::launched("k_norm"))) return rc;
+    if ((rc = launched("k_norm"))) return rc;
     // the bias corrections in double from the fp32 betas, as torch's Python scalars
     const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
     const float step_size = (float)((double)lr / bc1), bc2_sqrt = (float)sqrt(bc2);
     hipLaunchKernelGGL(train::k_adam, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, param, grad, exp_avg,
                        exp_avg_sq, n, sc + train::kNormBlocks, max_norm, beta1, beta2, step_size, bc2_sqrt, eps);
-    return train::launched("k_adam");
+    return launched("k_adam");
 }

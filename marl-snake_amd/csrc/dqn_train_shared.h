@@ -61,7 +61,6 @@ struct TrainScratch {
 };
 
 // dqn_train_kernels.hip
-int launched(const char *what);
 int reduce(const float *wpart, const float *bpart, int64_t chunks, int64_t nw, int64_t nb, float *wout, float *bout,
            hipStream_t s, const char *what);
 

@@ -14,6 +14,8 @@
 #include <tuple>
 #include <vector>
 
+#include <hip/hip_runtime.h>
+
 #include "snake_internal.h"
 
 #ifndef SNAKE_SPAWN_PRIO_SMALL   // (A/B builds: scripts/build_variants.sh)
@@ -36,6 +38,13 @@ void set_error(const char *fmt, ...)
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof g_err, fmt, ap);
     va_end(ap);
+}
+
+int launched(const char *what)
+{
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) { set_error("%s launch failed: %s", what, hipGetErrorString(err)); return SNAKE_E_LAUNCH; }
+    return SNAKE_OK;
 }
 
 static int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }

@@ -141,6 +141,8 @@ int layout_of(const snake_cfg *c, int64_t num_envs, snake_layout *out);
 int64_t fused_base(int64_t num_envs);
 int64_t fused_words(int64_t num_envs);
 void set_error(const char *fmt, ...);
+// after a kernel launch: SNAKE_OK, or SNAKE_E_LAUNCH and the error "<what> launch failed: <the runtime's message>"
+int launched(const char *what);
 
 // launchers (snake_kernels.hip)
 int launch_seed(const KCfg &k, const snake_state &st, uint32_t base_seed, int64_t env_offset,

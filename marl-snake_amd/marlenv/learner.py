@@ -10,11 +10,12 @@ include/snake_env.h). backward_precision='bf16' swaps the backward's GEMMs for
 their bf16 forms (dqn_train16_kernels.hip, snake_dqn32_backward_bf16). Nothing in update() syncs with the host.
 
 The master weights are the fp32 kernels' own layouts (snake_dqn32_net), so
-acting, the target forward and the update need no repacking: parameters,
-gradients and Adam's m and v are one flat float32 buffer each, the twelve
-tensors views into it at offsets padded to 64 bytes; the target net is a second
-flat buffer. state_dict(), grads() and checkpoint() convert to the reference's
-names and layouts with torch ops, off the hot path.
+acting, the target forward and the update need no repacking: parameters, target
+net, gradients and Adam's m and v are one dqn_weights.Net32 each -- a flat
+float32 buffer, the twelve tensors views into it at offsets padded to 64 bytes,
+and the struct of their addresses, built once. state_dict(), grads() and
+checkpoint() convert to the reference's names and layouts with torch ops
+(Net32.unpack), off the hot path.
 
 Acting with the weights in training goes through actor(): a bf16 DQNForward
 whose buffers snake_dqn_pack32 (dqn_pack_kernels.hip) refills from the master
@@ -24,39 +25,9 @@ import ctypes
 import weakref
 
 from ._device import get_torch as _torch, ptr, stream_ptr
-from ._native import ADAM_SCRATCH_BYTES, Dqn32Net, DqnCfg, check, lib
-from .dqn import DQNForward, _check_shapes, bf16_plan
-
-# snake_dqn32_net's field order, with the reference's parameter names
-FIELDS = ('conv1_w', 'conv2_w', 'conv3_w', 'fc1_w', 'fc2_w', 'fc3_w',
-          'conv1_b', 'conv2_b', 'conv3_b', 'fc1_b', 'fc2_b', 'fc3_b')
-NAMES = tuple(f[:-2] + ('.weight' if f.endswith('_w') else '.bias') for f in FIELDS)
-PAD = 16        # floats: every tensor starts at a multiple of 64 bytes
-
-
-def kernel_shapes(P, C, A):
-    """The twelve tensors' shapes in the kernel layouts, in FIELDS order."""
-    return ((32, 9 * C), (64, 288), (64, 576), (256, 64 * P), (128, 256), (A, 128),
-            (32,), (64,), (64,), (256,), (128,), (A,))
-
-
-def to_kernel(name, t, P):
-    """A reference-layout tensor (conv [out][in][3][3], fc1 columns ch*P + p) in
-    the kernel layout (conv [out][(tap, ci)], fc1 columns p*64 + ch)."""
-    if name.startswith('conv') and t.dim() == 4:
-        return t.permute(0, 2, 3, 1).reshape(t.shape[0], -1)
-    if name == 'fc1.weight':
-        return t.reshape(256, 64, P).permute(0, 2, 1).reshape(256, P * 64)
-    return t
-
-
-def from_kernel(name, t, P):
-    """The inverse of to_kernel (a new contiguous tensor)."""
-    if name.startswith('conv') and t.dim() == 2:
-        return t.reshape(t.shape[0], 3, 3, -1).permute(0, 3, 1, 2).contiguous()
-    if name == 'fc1.weight':
-        return t.reshape(256, P, 64).permute(0, 2, 1).reshape(256, 64 * P).contiguous()
-    return t.clone()
+from ._native import ADAM_SCRATCH_BYTES, DqnCfg, check, lib
+from .dqn import DQNForward, bf16_plan, forward32
+from .dqn_weights import FIELDS, NAMES, Net32, check_shapes, from_kernel, kernel_shapes, to_kernel  # noqa: F401
 
 
 class DQNLearner:
@@ -116,33 +87,24 @@ class DQNLearner:
         if backward_precision not in ('fp32', 'bf16'):
             raise ValueError("backward_precision must be 'fp32' or 'bf16'")
         self.backward_precision = backward_precision
-        _check_shapes(state, C, H * W, A)
+        check_shapes(state, C, H * W, A)
         if not (lr > 0.0 and eps >= 0.0 and max_grad_norm > 0.0 and 0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError('lr and max_grad_norm must be positive, eps >= 0, betas in [0, 1)')
         self.lr, self.gamma, self.betas, self.eps = float(lr), float(gamma), (float(betas[0]), float(betas[1])), float(eps)
         self.max_grad_norm = float(max_grad_norm)
         self.obs_shape = (H, W, C)
         self.num_actions = A
-        self._P = P = H * W
         if not torch.cuda.is_available():
             raise RuntimeError('DQNLearner needs a HIP device (MI355X); there is no CPU fallback')
         dev = torch.device(device) if device is not None else torch.device('cuda')
         if dev.index is None:
             dev = torch.device('cuda', torch.cuda.current_device())
         self.device = dev
-        self._shapes = kernel_shapes(P, C, A)
-        self._offsets, off = [], 0
-        for shape in self._shapes:
-            self._offsets.append(off)
-            size = shape[0] * (shape[1] if len(shape) == 2 else 1)
-            off += (size + PAD - 1) // PAD * PAD
-        self.numel = off
-
-        def flat():
-            return torch.zeros(self.numel, dtype=torch.float32, device=dev)
-
-        self._param, self._target, self._grad, self._m, self._v = flat(), flat(), flat(), flat(), flat()
-        self._net, self._tnet, self._gnet = (self._struct(b) for b in (self._param, self._target, self._grad))
+        # policy, target, gradient and Adam's m and v; and their flat buffers, which
+        # the Adam kernel and the target sync take whole
+        nets = self._pnet, self._tnet, self._gnet, self._mnet, self._vnet = [Net32(H * W, C, A, dev) for _ in range(5)]
+        self._param, self._target, self._grad, self._m, self._v = (n.flat for n in nets)
+        self.numel = self._pnet.numel
         self.step = 0
         self.grad_norm = torch.zeros((), dtype=torch.float32, device=dev)
         self.err = torch.zeros(1, dtype=torch.int32, device=dev)        # 1 once td_loss clamped an action
@@ -153,30 +115,8 @@ class DQNLearner:
         self._actors = weakref.WeakSet()        # the auto_sync actors, held weakly
         self._target16 = DQNForward.empty(H, W, C, A, device=dev, lib_path=lib_path) \
             if target_precision == 'bf16' else None
-        self._load(self._param, state)
+        self._pnet.load(state)
         self.sync_target()
-
-    # ------------------------------------------------------------ flat buffers
-    def _views(self, buf):
-        out = {}
-        for name, shape, off in zip(NAMES, self._shapes, self._offsets):
-            size = shape[0] * (shape[1] if len(shape) == 2 else 1)
-            out[name] = buf[off:off + size].view(shape)
-        return out
-
-    def _struct(self, buf):
-        base = buf.data_ptr()
-        return Dqn32Net(*(base + 4 * off for off in self._offsets))
-
-    def _load(self, buf, state):
-        torch = _torch()
-        _check_shapes(state, self.obs_shape[2], self._P, self.num_actions)
-        for name, view in self._views(buf).items():
-            t = state[name].detach().to(device=self.device, dtype=torch.float32)
-            view.copy_(to_kernel(name, t, self._P))
-
-    def _unpack(self, buf):
-        return {name: from_kernel(name, view, self._P) for name, view in self._views(buf).items()}
 
     def _buffer(self, key, nbytes):
         torch = _torch()
@@ -197,27 +137,19 @@ class DQNLearner:
         return obs.shape[0]
 
     def _forward(self, net, key, obs, features, who):
-        torch = _torch()
         B = self._check_obs(obs, who)
-        need = int(self._L.snake_dqn32_scratch(ctypes.byref(self.cfg), B))
-        check(need if need < 0 else 0, self._L)
-        scratch = self._buffer(key, need)
-        q = torch.empty((B, self.num_actions), dtype=torch.float32, device=self.device)
-        feat = torch.empty((B, 128), dtype=torch.float32, device=self.device) if features else None
-        with torch.cuda.device(self.device):
-            check(self._L.snake_dqn32_forward(ctypes.byref(self.cfg), ctypes.byref(net), ptr(obs), B, ptr(scratch),
-                                              ptr(q), ptr(feat), stream_ptr(self.device)), self._L)
+        q, feat, self._scratch[key] = forward32(self._L, self.cfg, net.struct, obs, self._scratch.get(key), features)
         if key == 'policy':
             self._fwd = (obs, B)
         return q, feat
 
     def __call__(self, obs):
         """The policy net's Q-values: uint8 (B, h, w, C) -> float32 (B, A)."""
-        return self._forward(self._net, 'policy', obs, False, '__call__')[0]
+        return self._forward(self._pnet, 'policy', obs, False, '__call__')[0]
 
     def forward_features(self, obs):
         """The policy net's relu(fc2): float32 (B, 128)."""
-        return self._forward(self._net, 'policy', obs, True, 'forward_features')[1]
+        return self._forward(self._pnet, 'policy', obs, True, 'forward_features')[1]
 
     def target_q(self, obs):
         """The target net's Q-values (with target_precision='bf16': the bf16
@@ -283,8 +215,8 @@ class DQNLearner:
         with torch.cuda.device(self.device):
             fn = self._L.snake_dqn32_backward_bf16 if self.backward_precision == 'bf16' \
                 else self._L.snake_dqn32_backward
-            check(fn(ctypes.byref(self.cfg), ctypes.byref(self._net), ptr(obs), B, ptr(self._scratch['policy']),
-                     ptr(dq), ptr(ts), ctypes.byref(self._gnet), stream_ptr(self.device)), self._L)
+            check(fn(ctypes.byref(self.cfg), ctypes.byref(self._pnet.struct), ptr(obs), B, ptr(self._scratch['policy']),
+                     ptr(dq), ptr(ts), ctypes.byref(self._gnet.struct), stream_ptr(self.device)), self._L)
         self._keep_dq = dq
 
     def apply(self):
@@ -315,7 +247,7 @@ class DQNLearner:
         """target_net.load_state_dict(policy_net.state_dict())."""
         self._target.copy_(self._param)
         if self._target16 is not None:
-            self._target16.pack32(self._tnet)
+            self._target16.pack32(self._tnet.struct)
 
     # ------------------------------------------------------------------ actors
     def actor(self, plan='auto', conv_waves=0, auto_sync=True):
@@ -336,7 +268,7 @@ class DQNLearner:
         a = DQNForward.empty(*self.obs_shape, num_actions=self.num_actions, device=self.device, plan=plan,
                              conv_waves=conv_waves, lib_path=self._lib_path)
         a._source = self
-        a.pack32(self._net)
+        a.pack32(self._pnet.struct)
         if auto_sync:
             self._actors.add(a)
         return a
@@ -345,39 +277,39 @@ class DQNLearner:
         """Repack an actor of this learner from the policy net, on the current stream."""
         if getattr(actor, '_source', None) is not self:
             raise ValueError('sync_actor takes a DQNForward made by this learner\'s actor()')
-        actor.pack32(self._net)
+        actor.pack32(self._pnet.struct)
 
     def _sync_actors(self):
         for a in list(self._actors):
-            a.pack32(self._net)
+            a.pack32(self._pnet.struct)
 
     def state_dict(self):
         """The policy net with the reference's names and layouts (copies)."""
-        return self._unpack(self._param)
+        return self._pnet.unpack()
 
     def target_state_dict(self):
-        return self._unpack(self._target)
+        return self._tnet.unpack()
 
     def grads(self):
         """The gradient buffer in the reference's layout (what .grad holds
         after loss.backward(), before the clip)."""
-        return self._unpack(self._grad)
+        return self._gnet.unpack()
 
     def checkpoint(self):
         """The learner's part of the reference's save_checkpoint (:356-383): both
         nets and Adam's state (step, exp_avg, exp_avg_sq by parameter name)."""
         return {'policy_net': self.state_dict(), 'target_net': self.target_state_dict(),
-                'optimizer': {'step': self.step, 'exp_avg': self._unpack(self._m),
-                              'exp_avg_sq': self._unpack(self._v)}}
+                'optimizer': {'step': self.step, 'exp_avg': self._mnet.unpack(),
+                              'exp_avg_sq': self._vnet.unpack()}}
 
     def load_checkpoint(self, ckpt):
         opt = ckpt['optimizer']
-        self._load(self._param, ckpt['policy_net'])
-        self._load(self._target, ckpt['target_net'])
-        self._load(self._m, opt['exp_avg'])
-        self._load(self._v, opt['exp_avg_sq'])
+        self._pnet.load(ckpt['policy_net'])
+        self._tnet.load(ckpt['target_net'])
+        self._mnet.load(opt['exp_avg'])
+        self._vnet.load(opt['exp_avg_sq'])
         self.step = int(opt['step'])
         self._fwd = None
         if self._target16 is not None:
-            self._target16.pack32(self._tnet)
+            self._target16.pack32(self._tnet.struct)
         self._sync_actors()

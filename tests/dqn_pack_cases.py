@@ -10,8 +10,9 @@ odd kept bit, one fp32 ulp either side of a tie, denormals, FLT_MIN, the
 infinities and FLT_MAX (which rounds to inf). No NaN: the comparisons are on
 bits, and a NaN's bits are not pinned.
 
-The ground truth is the packing DQNForward.__init__ has always done with torch
-ops, run on the CPU."""
+The ground truth is the torch packing of tests/dqn_pack_ref.py (what
+DQNForward.__init__ did before the library packed everything through
+snake_dqn_pack32), run on the CPU."""
 import ctypes
 import functools
 
@@ -78,11 +79,9 @@ def bits(t):
 
 
 def truth(state, plan, h, w, c, A):
-    """The bits of DQNForward(state, ..., device='cpu', plan=plan).tensors."""
-    from marlenv.dqn import DQNForward
-    f = DQNForward(state, h, w, c, num_actions=A, device='cpu', plan=plan)
-    assert f.plan == plan
-    return {k: bits(v) for k, v in f.tensors.items()}
+    """The bits of the torch packing (tests/dqn_pack_ref.py), run on the CPU."""
+    import dqn_pack_ref
+    return {k: bits(v) for k, v in dqn_pack_ref.torch_pack(state, plan, h, w, c, A).items()}
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,8 +1,9 @@
 """CPU checks of the pack (no GPU needed): snake_dqn_pack32_host -- the host
 twin that shares the kernel's index mappings and rounding -- against the torch
-packing of DQNForward.__init__ run on the CPU, bit for bit, on real-valued nets
-with the crafted rounding cases of tests/dqn_pack_cases.py; what the plans
-reject; the exports."""
+packing of tests/dqn_pack_ref.py run on the CPU, bit for bit, on real-valued nets
+with the crafted rounding cases of tests/dqn_pack_cases.py; the same for a
+DQNForward built from a state dict, which packs through the twin; what the
+plans reject; the exports."""
 import ctypes
 import os
 
@@ -96,6 +97,86 @@ def test_every_call_overwrites_everything(native):
     for state in (first, second):
         keep, net32 = PC.kernel_net(state, h, w)
         fwd.pack32(net32)
+    PC.assert_equal_bits(PC.packed_bits(fwd), want)
+
+
+def padding_is_zero(fwd):
+    """What 11x11x24 must show: channels padded to 32, 7 padding rows in 128,
+    all of them +0, and 0xFFFF nowhere."""
+    lay = fwd.layout
+    assert (lay.cpad, lay.k1, lay.p16) == (32, 288, 128)
+    for k in PC.BF16:
+        assert not bool((fwd.tensors[k] == -1).any()), k
+    # conv1 element (o, k): ((o/16 * K/32 + k/32) * 4 + (k%32)/8) * 128 + (o%16) * 8 + k%8
+    w1 = fwd.tensors['conv1_w']
+    for o, tap, ci in ((0, 0, 24), (17, 8, 31), (31, 4, 27)):
+        k = tap * 32 + ci
+        assert int(w1[((o // 16 * 9 + k // 32) * 4 + (k % 32) // 8) * 128 + (o % 16) * 8 + k % 8]) == 0
+    rows = fwd._rows.tolist()
+    assert rows.count(-1) == 7 and sorted(r for r in rows if r >= 0) == list(range(121))
+    fc1 = fwd.tensors['fc1_w'].view(256, 8, 2, 4, 16, 2, 4)      # n, m, half, quad, c16, j, r
+    for i, p in enumerate(rows):
+        if p < 0:
+            assert not bool(fc1[:, i // 16, :, (i % 16) // 4, :, :, i % 4].any()), i
+
+
+@pytest.mark.parametrize('plan,h,w,c,A', PC.CASES, ids=PC.IDS)
+def test_constructor_equals_the_torch_packing(native, plan, h, w, c, A):
+    """A DQNForward built from a state dict packs through the host twin into
+    buffers that are not zero-initialised: every bit is the model's."""
+    from marlenv.dqn import DQNForward
+    state, want = PC.case(plan, h, w, c, A)
+    fwd = DQNForward(state, h, w, c, num_actions=A, device='cpu', plan=plan)
+    assert fwd.plan == plan and fwd.precision == 'bf16' and fwd._source is None
+    PC.assert_equal_bits(PC.packed_bits(fwd), want, PC.IDS[PC.CASES.index((plan, h, w, c, A))])
+    if (plan, h, w, c) == ('window', 11, 11, 24):
+        padding_is_zero(fwd)
+
+
+def test_fp32_mode_holds_the_kernel_layout(native):
+    from marlenv.dqn import DQNForward
+    from marlenv.learner import FIELDS, NAMES, to_kernel
+    h, w, c, A = 3, 4, 8, 3
+    state = PC.real_state(h, w, c, A)
+    fwd = DQNForward(state, h, w, c, num_actions=A, precision='fp32', device='cpu')
+    assert fwd.plan is None and tuple(fwd.tensors) == FIELDS
+    for field, name in zip(FIELDS, NAMES):
+        t = fwd.tensors[field]
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0, field
+        assert torch.equal(PC.bits(t), PC.bits(to_kernel(name, state[name], h * w))), field
+        assert getattr(fwd.net, field) == t.data_ptr(), field
+    with pytest.raises(ValueError):
+        fwd.pack32(fwd.net)
+
+
+def test_constructor_packs_nan_to_nan(native):
+    """The NaN patterns of test_nan_packs_to_nan in a state dict: each bf16
+    tensor holds exactly four NaN and no infinity. Which quiet NaN a NaN becomes
+    is the pack's choice (bf16_rne in dqn_pack_kernels.hip) since the
+    constructor packs through it; it was torch's before. Their bits are not
+    pinned."""
+    from marlenv.dqn import DQNForward
+    state = PC.real_state(3, 3, 8, 3, crafted=False)
+    nans = torch.from_numpy(np.array([0x7f800001, 0x7fc00000, 0xffffffff, 0x7fffffff], np.uint32).view(np.float32))
+    for name in ('conv1.weight', 'conv2.weight', 'conv3.weight', 'fc1.weight', 'fc2.weight'):
+        state[name].view(-1)[:4] = nans
+        assert bool(state[name].view(-1)[:4].isnan().all())
+    fwd = DQNForward(state, 3, 3, 8, num_actions=3, device='cpu', plan='window')
+    for k in PC.BF16:
+        got = fwd.tensors[k].view(torch.bfloat16).float()
+        assert int(got.isnan().sum()) == 4, k
+        assert not bool(got.isinf().any()), k
+
+
+def test_pack32_on_a_state_built_forward(native):
+    """Every bf16 forward has the row table: pack32 replaces the weights of one
+    built from a state dict."""
+    from marlenv.dqn import DQNForward
+    h, w, c, A = 4, 6, 8, 3
+    fwd = DQNForward(PC.real_state(h, w, c, A, seed=1), h, w, c, num_actions=A, device='cpu', plan='map')
+    second, want = PC.case('map', h, w, c, A)
+    keep, net32 = PC.kernel_net(second, h, w)
+    fwd.pack32(net32)
     PC.assert_equal_bits(PC.packed_bits(fwd), want)
 
 

@@ -2,9 +2,10 @@
 (dqn_pack_kernels.hip; DQNForward.empty / pack32, DQNLearner.actor(),
 target_precision='bf16').
 
-k_dqn_pack must EQUAL the torch packing of DQNForward.__init__ run on the CPU,
+k_dqn_pack must EQUAL the torch packing of tests/dqn_pack_ref.py run on the CPU,
 bit for bit, on the real-valued nets of tests/dqn_pack_cases.py over 0xFF-filled
-buffers. An actor must hold exactly the packing of learner.state_dict() and give
+buffers; so must a DQNForward built from a state dict, which packs through the
+same kernel. An actor must hold exactly the packing of learner.state_dict() and give
 exactly the Q-values of a DQNForward built from it, after construction, after
 updates, after a checkpoint round trip; a bf16 target net the same for
 target_state_dict(). The default learner computes what it did, actor or none."""
@@ -35,6 +36,31 @@ def test_kernel_pack_equals_the_torch_packing(plan, h, w, c, A):
     PC.assert_equal_bits(first, want, 'first call')
     fwd.pack32(net32)
     PC.assert_equal_bits(PC.packed_bits(fwd), first, 'second call')
+
+
+@pytest.mark.parametrize('plan,h,w,c,A', [('window', 3, 3, 8, 3), ('window', 11, 11, 24, 4), ('map', 1, 7, 8, 3),
+                                          ('map', 20, 20, 8, 3)])
+def test_constructor_equals_the_torch_packing(plan, h, w, c, A):
+    """A DQNForward built from a state dict on the device: a transient fp32 net,
+    one launch of the pack kernel into uninitialised buffers."""
+    from marlenv.dqn import DQNForward
+    state, want = PC.case(plan, h, w, c, A)
+    fwd = DQNForward(state, h, w, c, num_actions=A, device=DEV, plan=plan)
+    assert fwd.plan == plan and fwd._source is None
+    PC.assert_equal_bits(PC.packed_bits(fwd), want)
+
+
+def test_constructor_and_empty_pack32_give_the_same_q():
+    from marlenv.dqn import DQNForward
+    state = PC.real_state(5, 5, 8, 3, crafted=False)
+    obs = P.probe_obs(70, 5, 5, 8, 3).to(DEV)
+    built = DQNForward(state, 5, 5, 8, device=DEV)
+    filled = DQNForward.empty(5, 5, 8, device=DEV)
+    keep, net32 = PC.kernel_net(state, 5, 5, DEV)
+    filled.pack32(net32)
+    q, want = built(obs), filled(obs)
+    assert bool(torch.isfinite(want).all()) and float(want.abs().max()) > 0
+    assert torch.equal(q, want)
 
 
 def test_nan_packs_to_nan():
