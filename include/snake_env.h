@@ -426,6 +426,36 @@ int snake_dqn32_backward_bf16(const snake_dqn_cfg *cfg, const snake_dqn32_net *n
                               int64_t batch, const void *fwd_scratch, const float *dq, void *train_scratch,
                               const snake_dqn32_net *grad, void *stream);
 
+/* snake_dqn32_forward in bf16 mixed precision (dqn_fwd16_kernels.hip), the
+ * learner's training forward: the same arguments, preconditions, return codes
+ * and error texts as snake_dqn32_forward, on every geometry it accepts (no
+ * dispatch by map width); batch == 0 returns SNAKE_OK. The weights are the fp32
+ * masters, the activations are stored fp32.
+ *   conv1, conv2, conv3, fc1 and fc2 run on v_mfma_f32_16x16x32_bf16:
+ *     Y[m][n] = sum_k bf16(act(X)[m][k]) * bf16(W[n][k])
+ *   act(X) is formed in fp32 first, exactly as the fp32 forward and the bf16
+ *   weight gradient form it: the byte, or byte / 255 when the flag is set;
+ *   relu(Y_prev + b_prev) otherwise (zero outside the map). bf16() is round to
+ *   nearest even, the hardware's v_cvt_pk_bf16_f32, as in
+ *   snake_dqn32_backward_bf16. Products are exact and sums are fp32.
+ * Not rounded: Y as it is stored (the fp32 sum); the biases; the flag kernel;
+ * fc3 (the fp32 forward's kernel on fp32 relu(Y5 + b) and fp32 weights);
+ * feat_out = relu(Y5 + b) in fp32.
+ * Scratch: snake_dqn32_forward_bf16_scratch(cfg, batch) bytes >=
+ * snake_dqn32_scratch(cfg, batch). It begins with exactly snake_dqn32_forward's
+ * layout -- the flag (16 bytes), then Y1..Y5, fp32 pre-activations without
+ * bias, NHWC -- so snake_dqn32_backward and snake_dqn32_backward_bf16 take it
+ * as fwd_scratch unchanged; fc1's split-K partials follow.
+ * Split K: the K reduction steps of fc1 (K = 64 h w) and fc2 (K = 256) are cut
+ * into chunks of max(1024, ceil(K / 16) rounded up to 64) steps; with more than
+ * one chunk each writes a partial [chunk][B][N] and a second kernel adds the
+ * partials in chunk order. The rule depends on K alone: a row's results do not
+ * depend on the batch it is in. No floating-point atomics; every summation
+ * order is a function of the shape alone, results are bitwise reproducible. */
+int64_t snake_dqn32_forward_bf16_scratch(const snake_dqn_cfg *cfg, int64_t batch);   /* bytes, < 0 on error */
+int snake_dqn32_forward_bf16(const snake_dqn_cfg *cfg, const snake_dqn32_net *net, const uint8_t *obs,
+                             int64_t batch, void *scratch, float *q_out, float *feat_out, void *stream);
+
 /* The TD loss (:243-250), one launch. Per row b, in fp32 and in this order:
  *   target = reward[b] + ((1 - done[b]) * gamma) * max_a next_q[b][a]
  *   d      = q[b][action[b]] - target

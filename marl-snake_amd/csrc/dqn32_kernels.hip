@@ -25,6 +25,10 @@
 // Layers store pre-activations; the last adds fc3's bias, forward_features is
 // relu(fc2 + bias). Scratch: Y1 [B*P][32], Y2, Y3 [B*P][64], Y4 [B][256],
 // Y5 [B][128] fp32 + a 16-byte flag word (snake_dqn32_scratch).
+//
+// snake_dqn32_forward_bf16 is the same launch sequence with the five GEMMs of
+// the matrix cores handed to dqn_fwd16_kernels.hip (bf16 operands, fp32 sums);
+// the flag kernel, fc3 and the features are the launches below.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -633,22 +637,28 @@ extern "C" int64_t snake_dqn32_scratch(const snake_dqn_cfg *cfg, int64_t batch)
     return dqn32::scratch_bytes(cfg, batch, nullptr, nullptr);
 }
 
-extern "C" int snake_dqn32_forward(const snake_dqn_cfg *cfg, const snake_dqn32_net *net, const uint8_t *obs,
-                                   int64_t batch, void *scratch, float *q_out, float *feat_out, void *stream)
+// The forward of both precisions: one validation and one launch sequence. With
+// bf16 the five GEMMs of the matrix cores go to dqn_fwd16_kernels.hip's kernel
+// (any map width, fc1 split along K); the flag kernel, fc3 and the features are
+// the same launches.
+static int forward(const char *who, bool bf16, const snake_dqn_cfg *cfg, const snake_dqn32_net *net,
+                   const uint8_t *obs, int64_t batch, void *scratch, float *q_out, float *feat_out, void *stream)
 {
     int rc = dqn32::check_cfg(cfg);
     if (rc) return rc;
     if (!net || !obs || !scratch || !q_out || !net->conv1_w || !net->conv2_w || !net->conv3_w || !net->fc1_w ||
         !net->fc2_w || !net->fc3_w || !net->conv1_b || !net->conv2_b || !net->conv3_b || !net->fc1_b ||
         !net->fc2_b || !net->fc3_b) {
-        set_error("snake_dqn32_forward: NULL buffer");
+        set_error("%s: NULL buffer", who);
         return SNAKE_E_ARG;
     }
-    if (batch < 0) { set_error("snake_dqn32_forward: batch < 0"); return SNAKE_E_ARG; }
+    if (batch < 0) { set_error("%s: batch < 0", who); return SNAKE_E_ARG; }
     if (batch == 0) return SNAKE_OK;
     const hipStream_t s = (hipStream_t)stream;
     dqn32::Scratch sc;
-    dqn32::scratch_bytes(cfg, batch, scratch, &sc);
+    float *partials = nullptr;
+    if (bf16) dqn32::fwd16_scratch_bytes(cfg, batch, scratch, &sc, &partials);
+    else dqn32::scratch_bytes(cfg, batch, scratch, &sc);
     const int H = cfg->height, W = cfg->width, C = cfg->channels, A = cfg->num_actions;
     const int64_t P = (int64_t)H * W, BP = batch * P;
     if (hipMemsetAsync(sc.flag, 0, 16, s) != hipSuccess) { set_error("snake_dqn32: memset failed"); return SNAKE_E_LAUNCH; }
@@ -666,26 +676,32 @@ extern "C" int snake_dqn32_forward(const snake_dqn_cfg *cfg, const snake_dqn32_n
     // conv1: uint8 NHWC obs -> Y1 [B*P][32]
     g.x = obs; g.xbias = nullptr; g.w = net->conv1_w; g.y = sc.y1; g.ybias = nullptr;
     g.M = BP; g.N = 32; g.K = 9 * C; g.C = C; g.scale_flag = sc.flag;
-    if ((rc = mfma ? dqn32::conv_mfma<dqn32::kConvU8, 2>(g, s, "conv1") : dqn32::gemm<dqn32::kConvU8>(g, s, "conv1")))
+    if ((rc = bf16   ? dqn32::gemm16(dqn32::kConvU8, g, partials, s, "conv1")
+              : mfma ? dqn32::conv_mfma<dqn32::kConvU8, 2>(g, s, "conv1")
+                     : dqn32::gemm<dqn32::kConvU8>(g, s, "conv1")))
         return rc;
     // conv2: relu(Y1 + b1) -> Y2 [B*P][64]
     g.x = sc.y1; g.xbias = net->conv1_b; g.w = net->conv2_w; g.y = sc.y2;
     g.N = 64; g.K = 9 * 32; g.C = 32;
-    if ((rc = mfma ? dqn32::conv_mfma<dqn32::kConvF32, 4>(g, s, "conv2") : dqn32::gemm<dqn32::kConvF32>(g, s, "conv2")))
+    if ((rc = bf16   ? dqn32::gemm16(dqn32::kConvF32, g, partials, s, "conv2")
+              : mfma ? dqn32::conv_mfma<dqn32::kConvF32, 4>(g, s, "conv2")
+                     : dqn32::gemm<dqn32::kConvF32>(g, s, "conv2")))
         return rc;
     // conv3: relu(Y2 + b2) -> Y3
     g.x = sc.y2; g.xbias = net->conv2_b; g.w = net->conv3_w; g.y = sc.y3;
     g.N = 64; g.K = 9 * 64; g.C = 64;
-    if ((rc = mfma ? dqn32::conv_mfma<dqn32::kConvF32, 4>(g, s, "conv3") : dqn32::gemm<dqn32::kConvF32>(g, s, "conv3")))
+    if ((rc = bf16   ? dqn32::gemm16(dqn32::kConvF32, g, partials, s, "conv3")
+              : mfma ? dqn32::conv_mfma<dqn32::kConvF32, 4>(g, s, "conv3")
+                     : dqn32::gemm<dqn32::kConvF32>(g, s, "conv3")))
         return rc;
     // fc1: relu(Y3 + b3) flattened NHWC (P*64) -> Y4 [B][256]
     g.x = sc.y3; g.xbias = net->conv3_b; g.bmod = 64; g.w = net->fc1_w; g.y = sc.y4;
     g.M = batch; g.N = 256; g.K = (int)(P * 64);
-    if ((rc = dqn32::fc_mfma(g, s, "fc1"))) return rc;
+    if ((rc = bf16 ? dqn32::gemm16(dqn32::kDense, g, partials, s, "fc1") : dqn32::fc_mfma(g, s, "fc1"))) return rc;
     // fc2: relu(Y4 + bfc1) -> Y5 [B][128]
     g.x = sc.y4; g.xbias = net->fc1_b; g.bmod = 256; g.w = net->fc2_w; g.y = sc.y5;
     g.N = 128; g.K = 256;
-    if ((rc = dqn32::fc_mfma(g, s, "fc2"))) return rc;
+    if ((rc = bf16 ? dqn32::gemm16(dqn32::kDense, g, partials, s, "fc2") : dqn32::fc_mfma(g, s, "fc2"))) return rc;
     // fc3: relu(Y5 + bfc2) -> q [B][A] + bfc3
     g.x = sc.y5; g.xbias = net->fc2_b; g.bmod = 128; g.w = net->fc3_w; g.y = q_out; g.ybias = net->fc3_b;
     g.N = A; g.K = 128;
@@ -697,4 +713,24 @@ extern "C" int snake_dqn32_forward(const snake_dqn_cfg *cfg, const snake_dqn32_n
         if ((rc = launched("k_bias_relu"))) return rc;
     }
     return SNAKE_OK;
+}
+
+extern "C" int snake_dqn32_forward(const snake_dqn_cfg *cfg, const snake_dqn32_net *net, const uint8_t *obs,
+                                   int64_t batch, void *scratch, float *q_out, float *feat_out, void *stream)
+{
+    return forward("snake_dqn32_forward", false, cfg, net, obs, batch, scratch, q_out, feat_out, stream);
+}
+
+extern "C" int64_t snake_dqn32_forward_bf16_scratch(const snake_dqn_cfg *cfg, int64_t batch)
+{
+    const int rc = dqn32::check_cfg(cfg);
+    if (rc) return rc;
+    if (batch < 0) { set_error("snake_dqn32_forward_bf16_scratch: batch < 0"); return SNAKE_E_ARG; }
+    return dqn32::fwd16_scratch_bytes(cfg, batch, nullptr, nullptr, nullptr);
+}
+
+extern "C" int snake_dqn32_forward_bf16(const snake_dqn_cfg *cfg, const snake_dqn32_net *net, const uint8_t *obs,
+                                        int64_t batch, void *scratch, float *q_out, float *feat_out, void *stream)
+{
+    return forward("snake_dqn32_forward_bf16", true, cfg, net, obs, batch, scratch, q_out, feat_out, stream);
 }

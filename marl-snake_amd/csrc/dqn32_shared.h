@@ -1,7 +1,8 @@
 // dqn32_shared.h -- what the fp32 forward (dqn32_kernels.hip) and the learner
 // (dqn_train_kernels.hip) share: the GEMM argument block and its operand modes,
-// the configuration check, the forward's scratch layout and the LDS patch sizes
-// (not part of the C-ABI).
+// the configuration check, the forward's scratch layout and the LDS patch sizes,
+// and the bf16 forward's (dqn_fwd16_kernels.hip) split-K rule, scratch and
+// launch helper (not part of the C-ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -88,6 +89,32 @@ inline int64_t scratch_bytes(const snake_dqn_cfg *cfg, int64_t B, void *base, Sc
     }
     return 16 + 4 * (n1 + n2 + n3 + n4 + n5);
 }
+
+// ---- the bf16 mixed-precision forward (dqn_fwd16_kernels.hip)
+// Split K of its dense layers: the K reduction steps are cut into chunks of
+// max(1024, ceil(K / 16) rounded up to 64) steps -- at most 16 chunks, a rule of
+// K alone, so a row's sums do not depend on the batch it is in.
+constexpr int kSplitMinK = 1024, kSplitMaxChunks = 16;
+__host__ __device__ inline int split_k_chunk(int K)
+{
+    const int c = ((K + kSplitMaxChunks - 1) / kSplitMaxChunks + 63) / 64 * 64;
+    return c > kSplitMinK ? c : kSplitMinK;
+}
+inline int split_k_chunks(int K) { return K < 1 ? 1 : (K + split_k_chunk(K) - 1) / split_k_chunk(K); }
+
+// its scratch: dqn32::Scratch's layout, then fc1's split-K partials [chunks][B][256]
+// (none with one chunk; fc2's K = 256 is one chunk)
+inline int64_t fwd16_scratch_bytes(const snake_dqn_cfg *cfg, int64_t B, void *base, Scratch *out, float **partials)
+{
+    const int64_t head = scratch_bytes(cfg, B, base, out);
+    const int chunks = split_k_chunks(cfg->height * cfg->width * 64);
+    if (partials) *partials = reinterpret_cast<float *>(reinterpret_cast<uint8_t *>(base) + head);
+    return head + (chunks > 1 ? 4 * (int64_t)chunks * B * 256 : 0);
+}
+
+// Y = bf16(act(X)) bf16(W)^T of one layer (mode: kConvU8, kConvF32 or kDense; ybias unused);
+// partials: room for the dense layers' split-K partials [chunks][M][N]
+int gemm16(int mode, const GemmArgs &g, float *partials, hipStream_t s, const char *what);
 
 }  // namespace dqn32
 }  // namespace snake

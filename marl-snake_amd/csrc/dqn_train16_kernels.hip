@@ -36,6 +36,7 @@
 
 #include <stdint.h>
 
+#include "dqn_bf16_tile.h"
 #include "dqn_train_shared.h"
 
 namespace snake {
@@ -45,74 +46,12 @@ using dqn32::kConvF32;
 using dqn32::kConvU8;
 using dqn32::kDense;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kKT16 = 64;       // reduction steps per LDS stage
-constexpr int kRowB = 128;      // bytes of an LDS row: kKT16 bf16
-
-// Two floats to two bf16 in one word, lo in the low half: the conversion
-// instruction of gfx950 (v_cvt_pk_bf16_f32), which is what the compiler emits
-// for a float -> __bf16 conversion. Round to nearest even, the value
-// dqn_kernels.hip bf16_bits computes on the bit pattern (denormals are kept);
-// a NaN stays a NaN: sign and top mantissa bits kept, the quiet bit set, as in
-// the pack (dqn_pack_kernels.hip bf16_rne). In software the two additions,
-// shifts and the NaN test per element made the loaders longer than the MFMAs.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pack2(float lo, float hi)
-{
-    const f32x2 v = {lo, hi};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
+// (pack2, xcd_remap, swz, slot_off and mma64: dqn_bf16_tile.h, shared with the bf16 forward)
 
 // p / w for 0 <= p < 2^16 and 1 <= w <= 255 with a quotient below 256: the
 // product's error is below 2^-13, the distance of (p + 0.5) / w to an integer at
 // least 0.5 / 255
 __device__ __forceinline__ int div_small(int p, float rcp_w) { return (int)(((float)p + 0.5f) * rcp_w); }
-
-// Workgroups are dealt to the eight XCDs (private L2s) round-robin by their
-// linear id: neighbours in the grid, which share an operand panel (the column
-// tiles of a weight gradient's chunk its dY rows, the row tiles of an input
-// gradient's column tile its W columns), each fetch it into another L2. Renumber
-// so that XCD j's workgroups j, j + 8, ... take consecutive tiles. A bijection
-// of [0, nwg): a matter of speed only, every tile is computed once wherever it
-// runs.
-__device__ __forceinline__ uint32_t xcd_remap(uint32_t bid, uint32_t nwg)
-{
-    const uint32_t j = bid & 7, q = nwg >> 3, r = nwg & 7;
-    return j * q + (j < r ? j : r) + (bid >> 3);
-}
-
-// the slot swizzle of LDS row r (see the head of the file)
-__device__ __forceinline__ int swz(int r)
-{
-    const int u = (r >> 2) & 3, v = r & 3;
-    return (((u ^ (u >> 1)) & 1) ^ (2 * u + (v >> 1)) ^ (v & 1) ^ ((r >> 4) & 1)) & 7;
-}
-__device__ __forceinline__ int slot_off(int r, int s) { return r * kRowB + ((s ^ swz(r)) << 4); }
-
-// 64 reduction steps of the workgroup's LDS tiles into this wave's 2 x 2 tiles
-__device__ __forceinline__ void mma64(const uint8_t *As, const uint8_t *Bs, int wr, int wc, int grp, int l16,
-                                      f32x4 (&acc)[2][2])
-{
-#pragma unroll
-    for (int ks = 0; ks < 2; ks++) {
-        bf16x8 a[2], b[2];
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            a[i] = *reinterpret_cast<const bf16x8 *>(As + slot_off(wr * 32 + i * 16 + l16, 4 * ks + grp));
-            b[i] = *reinterpret_cast<const bf16x8 *>(Bs + slot_off(wc * 32 + i * 16 + l16, 4 * ks + grp));
-        }
-#pragma unroll
-        for (int i = 0; i < 2; i++)
-#pragma unroll
-            for (int c = 0; c < 2; c++)
-                acc[i][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[c], acc[i][c], 0, 0, 0);
-    }
-}
 
 // reduction steps 4kk .. 4kk+3 (v[0..3]) of rows q4 .. q4+3 (the vector's elements), transposed into the image
 __device__ __forceinline__ void stage_transposed(uint8_t *S, int kk, int q4, const f32x4 (&v)[4])

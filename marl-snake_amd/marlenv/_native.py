@@ -22,7 +22,8 @@ EXPORTS = ('snake_plan', 'snake_plan_paths', 'snake_build_candidates', 'snake_se
            'snake_genome_plan', 'snake_genome_check', 'snake_genome_tiles', 'snake_genome_actions',
            'snake_graph_plan', 'snake_graph_weights', 'snake_graph_obs',
            'snake_dqn32_train_scratch', 'snake_dqn32_backward', 'snake_dqn_td_loss', 'snake_adam_step',
-           'snake_dqn_pack32', 'snake_dqn_pack32_host', 'snake_dqn32_backward_bf16')
+           'snake_dqn_pack32', 'snake_dqn_pack32_host', 'snake_dqn32_backward_bf16',
+           'snake_dqn32_forward_bf16_scratch', 'snake_dqn32_forward_bf16')
 
 ADAM_SCRATCH_BYTES = 4112       # SNAKE_ADAM_SCRATCH_BYTES
 
@@ -188,6 +189,9 @@ def lib(path=None):
     L.snake_dqn32_backward.argtypes = [ctypes.POINTER(DqnCfg), ctypes.POINTER(Dqn32Net), P, I64, P, P, P,
                                        ctypes.POINTER(Dqn32Net), P]
     L.snake_dqn32_backward_bf16.argtypes = L.snake_dqn32_backward.argtypes
+    L.snake_dqn32_forward_bf16_scratch.argtypes = L.snake_dqn32_scratch.argtypes
+    L.snake_dqn32_forward_bf16_scratch.restype = I64
+    L.snake_dqn32_forward_bf16.argtypes = L.snake_dqn32_forward.argtypes
     F32 = ctypes.c_float
     L.snake_dqn_td_loss.argtypes = [P, P, P, P, P, I64, ctypes.c_int32, F32, P, P, P, P]
     L.snake_adam_step.argtypes = [P, P, P, P, I64, I64, F32, F32, F32, F32, F32, P, P, P]

@@ -83,6 +83,16 @@ def forward32(L, cfg, net, obs, scratch, features):
     return launch_forward(L, L.snake_dqn32_forward, cfg, net, obs, scratch, scratch32(L, cfg, obs.shape[0]), features)
 
 
+def forward32_bf16(L, cfg, net, obs, scratch, features):
+    """The same forward in bf16 mixed precision (snake_dqn32_forward_bf16: the
+    fp32 weights and stored activations, GEMM operands rounded to bf16 as they
+    are staged), with its own scratch size; what DQNLearner runs with
+    forward_precision='bf16' and target_precision='mixed'."""
+    need = int(L.snake_dqn32_forward_bf16_scratch(ctypes.byref(cfg), obs.shape[0]))
+    check(need if need < 0 else 0, L)
+    return launch_forward(L, L.snake_dqn32_forward_bf16, cfg, net, obs, scratch, need, features)
+
+
 class DQNForward:
     """DQN(input_shape=(N, h, w, c), num_actions) forward on uint8 NHWC observations.
 

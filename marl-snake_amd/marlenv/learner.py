@@ -7,7 +7,11 @@ fp32 on the device: the forward of dqn32_kernels.hip, and the backward pass, TD
 loss and clip + Adam of dqn_train_kernels.hip (snake_dqn32_backward,
 snake_dqn_td_loss, snake_adam_step; the exact semantics are in
 include/snake_env.h). backward_precision='bf16' swaps the backward's GEMMs for
-their bf16 forms (dqn_train16_kernels.hip, snake_dqn32_backward_bf16). Nothing in update() syncs with the host.
+their bf16 forms (dqn_train16_kernels.hip, snake_dqn32_backward_bf16), and
+forward_precision='bf16' the policy forward's (dqn_fwd16_kernels.hip,
+snake_dqn32_forward_bf16: the same scratch, so either backward follows either
+forward); target_precision='mixed' runs the target forward through the same
+function. Nothing in update() syncs with the host.
 
 The master weights are the fp32 kernels' own layouts (snake_dqn32_net), so
 acting, the target forward and the update need no repacking: parameters, target
@@ -26,7 +30,7 @@ import weakref
 
 from ._device import get_torch as _torch, ptr, stream_ptr
 from ._native import ADAM_SCRATCH_BYTES, DqnCfg, check, lib
-from .dqn import DQNForward, bf16_plan, forward32
+from .dqn import DQNForward, bf16_plan, forward32, forward32_bf16
 from .dqn_weights import FIELDS, NAMES, Net32, check_shapes, from_kernel, kernel_shapes, to_kernel  # noqa: F401
 
 
@@ -56,7 +60,20 @@ class DQNLearner:
     (w+2) <= 576) and raise ValueError with the plan's message, before any
     device work, where none does. The bf16 forward reads the observations as
     0/1 bytes: unlike the fp32 forward it does not take the reference's /255
-    branch.
+    branch. target_precision='mixed' runs target_q on the fp32 target buffer
+    through snake_dqn32_forward_bf16 instead (see forward_precision): no packed
+    copy, any geometry, the /255 branch included.
+
+    forward_precision='bf16' runs learner(obs) and forward_features(obs) -- so
+    update()'s policy forward -- through snake_dqn32_forward_bf16: the five
+    GEMMs of the matrix cores on the bf16 matrix cores, their operands (act(X)
+    formed in fp32, and the fp32 master weights) rounded to bf16 as they are
+    staged, fp32 sums, the pre-activations stored fp32 where either backward
+    reads them; fc3 and the features stay fp32 (the rounding points are in
+    include/snake_env.h). Any geometry the fp32 forward accepts. The default
+    'fp32' launches exactly what it did without the option.
+    pre_activations() returns fp32 copies of the last policy forward's
+    Y1..Y5 (without bias, NHWC), in both modes, off the hot path.
 
     backward_precision='bf16' runs backward() -- so update()'s -- weight and
     input gradients on the bf16 matrix cores (snake_dqn32_backward_bf16: the
@@ -65,11 +82,12 @@ class DQNLearner:
     Adam, grads(), state_dict(), checkpoint() and actor() are the same in both
     modes, a checkpoint of one loads into the other, and the default 'fp32'
     computes exactly what it did without the option. Any geometry the fp32
-    backward accepts."""
+    backward accepts. The same holds across forward_precision and
+    target_precision: a checkpoint of any mode loads into any other."""
 
     def __init__(self, state, height, width, channels, num_actions=3, lr=5e-4, gamma=0.99, betas=(0.9, 0.999),
                  eps=1e-8, max_grad_norm=10.0, device=None, lib_path=None, target_precision='fp32',
-                 backward_precision='fp32'):
+                 backward_precision='fp32', forward_precision='fp32'):
         torch = _torch()
         if hasattr(state, 'state_dict'):
             state = state.state_dict()
@@ -79,14 +97,17 @@ class DQNLearner:
         self.cfg = DqnCfg(H, W, C, A, 0)
         n = L.snake_dqn32_train_scratch(ctypes.byref(self.cfg), 0)      # ValueError before any device work
         check(int(n) if n < 0 else 0, L)
-        if target_precision not in ('fp32', 'bf16'):
-            raise ValueError("target_precision must be 'fp32' or 'bf16'")
+        if target_precision not in ('fp32', 'bf16', 'mixed'):
+            raise ValueError("target_precision must be 'fp32', 'bf16' or 'mixed'")
         if target_precision == 'bf16':
             bf16_plan(L, self.cfg)
         self.target_precision = target_precision
         if backward_precision not in ('fp32', 'bf16'):
             raise ValueError("backward_precision must be 'fp32' or 'bf16'")
         self.backward_precision = backward_precision
+        if forward_precision not in ('fp32', 'bf16'):
+            raise ValueError("forward_precision must be 'fp32' or 'bf16'")
+        self.forward_precision = forward_precision
         check_shapes(state, C, H * W, A)
         if not (lr > 0.0 and eps >= 0.0 and max_grad_norm > 0.0 and 0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError('lr and max_grad_norm must be positive, eps >= 0, betas in [0, 1)')
@@ -138,7 +159,9 @@ class DQNLearner:
 
     def _forward(self, net, key, obs, features, who):
         B = self._check_obs(obs, who)
-        q, feat, self._scratch[key] = forward32(self._L, self.cfg, net.struct, obs, self._scratch.get(key), features)
+        mixed = self.forward_precision == 'bf16' if key == 'policy' else self.target_precision == 'mixed'
+        q, feat, self._scratch[key] = (forward32_bf16 if mixed else forward32)(
+            self._L, self.cfg, net.struct, obs, self._scratch.get(key), features)
         if key == 'policy':
             self._fwd = (obs, B)
         return q, feat
@@ -151,9 +174,30 @@ class DQNLearner:
         """The policy net's relu(fc2): float32 (B, 128)."""
         return self._forward(self._pnet, 'policy', obs, True, 'forward_features')[1]
 
+    def pre_activations(self):
+        """{'Y1'..'Y5'}: float32 copies of the pre-activations (without bias) the
+        last policy forward left in its scratch, shaped (B, h, w, 32), (B, h, w,
+        64), (B, h, w, 64), (B, 256) and (B, 128). ValueError before any policy
+        forward."""
+        torch = _torch()
+        if self._fwd is None:
+            raise ValueError('pre_activations needs a policy forward (call learner(obs) first)')
+        B, (H, W, _) = self._fwd[1], self.obs_shape
+        flat = self._scratch['policy'][16:].view(torch.float32)
+        out, at = {}, 0
+        for name, shape in (('Y1', (B, H, W, 32)), ('Y2', (B, H, W, 64)), ('Y3', (B, H, W, 64)), ('Y4', (B, 256)),
+                            ('Y5', (B, 128))):
+            n = 1
+            for d in shape:
+                n *= d
+            out[name] = flat[at:at + n].view(shape).clone()
+            at += n
+        return out
+
     def target_q(self, obs):
         """The target net's Q-values (with target_precision='bf16': the bf16
-        forward on the packed copy of the target net)."""
+        forward on the packed copy of the target net; with 'mixed': the bf16
+        mixed-precision forward on the fp32 target buffer)."""
         if self._target16 is not None:
             self._check_obs(obs, 'target_q')
             return self._target16(obs)

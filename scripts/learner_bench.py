@@ -28,6 +28,15 @@ their fraction of the 2.5 PF bf16 peak). --backward-precision both times
 backward and update of an fp32-mode and a bf16-mode learner in one process on
 the same batches, by the same method, and writes the record to
 profiles/learner_bf16_bench.json (or --out).
+
+--forward-precision bf16 builds the learner with forward_precision='bf16' and
+target_precision='mixed' (also for --trace-loop; --fold-trace labels the
+k_fwd16 dispatches of an update by layer, target forward first, and adds their
+FLOPs). --forward-precision both times the policy forward, the target forward
+(fp32 against 'mixed') and update of an fp32-forward and a bf16-forward learner
+in one process on the same batches, by the same method, with
+--backward-precision fp32 or bf16 for both, and writes the record to
+profiles/learner_fwd16_bench.json (or --out).
 """
 import argparse
 import csv
@@ -42,6 +51,7 @@ sys.path.insert(0, os.path.join(ROOT, 'marl-snake_amd'))
 FP32_MATRIX_PEAK = 157.3e12
 BF16_MATRIX_PEAK = 2.5e15
 BF16_RECORD = os.path.join(ROOT, 'profiles', 'learner_bf16_bench.json')
+FWD16_RECORD = os.path.join(ROOT, 'profiles', 'learner_fwd16_bench.json')
 SHAPES = {'config_20x20x8': (20, 20, 8), 'vision5_11x11x8': (11, 11, 8)}
 BATCH = 512
 
@@ -57,6 +67,13 @@ def gemm_flops(h, w, c, A=3, B=BATCH):
         'wgrad conv2': 2 * M * 64 * 288, 'dgrad conv2': 2 * M * 32 * 576,
         'wgrad conv1': 2 * M * 32 * 9 * c,
     }
+
+
+def forward_gemm_flops(h, w, c, B=BATCH):
+    """Algorithmic FLOPs of one forward's five matrix-core GEMMs, by layer."""
+    M = B * h * w
+    return {'conv1': 2 * M * 32 * 9 * c, 'conv2': 2 * M * 64 * 288, 'conv3': 2 * M * 64 * 576,
+            'fc1': 2 * B * 256 * 64 * h * w, 'fc2': 2 * B * 128 * 256}
 
 
 def update_bytes(h, w, c, A=3, B=BATCH):
@@ -116,8 +133,22 @@ def fold_trace(path, updates, shape):
                             'frac_of_fp32_matrix_peak': f / (e['median_us'] * 1e-6) / FP32_MATRIX_PEAK}
             if is16:
                 gemms[layer]['frac_of_bf16_matrix_peak'] = f / (e['median_us'] * 1e-6) / BF16_MATRIX_PEAK
+    # the bf16 forward's GEMMs: k_fwd16<0> conv1, <1> conv2, conv3, <2> fc1, fc2; with a 'mixed' target an
+    # update runs them twice, the target forward first
+    fwd, fflops = {}, forward_gemm_flops(h, w, c)
+    for label, e in out.items():
+        base = label.split(' #')[0]
+        j = int(label.split('#')[1]) if '#' in label else 0
+        for arg, layers in (('0', ('conv1',)), ('1', ('conv2', 'conv3')), ('2', ('fc1', 'fc2'))):
+            if base.startswith('k_fwd16<%s>' % arg) or base.startswith('k_fwd16<(int)%s>' % arg):
+                per = sum(1 for x in out if x.split(' #')[0] == base)
+                who = ('target', 'policy')[j // len(layers)] if per == 2 * len(layers) else 'policy'
+                f = fflops[layers[j % len(layers)]]
+                fwd['%s %s' % (who, layers[j % len(layers)])] = {
+                    'median_us': e['median_us'], 'flops': f, 'tflops': f / (e['median_us'] * 1e-6) / 1e12,
+                    'frac_of_bf16_matrix_peak': f / (e['median_us'] * 1e-6) / BF16_MATRIX_PEAK}
     return {'shape': shape, 'updates_traced': updates, 'kernels_us': out, 'backward_gemms': gemms,
-            'order_in_backward': order}
+            'forward_gemms': fwd, 'order_in_backward': order}
 
 
 def main():
@@ -134,13 +165,16 @@ def main():
     ap.add_argument('--record', default=None, help='--fold-trace: the JSON record to add the kernels to')
     ap.add_argument('--backward-precision', default='fp32', choices=('fp32', 'bf16', 'both'),
                     help="the learner's backward_precision; both: backward and update in each mode, side by side")
+    ap.add_argument('--forward-precision', default='fp32', choices=('fp32', 'bf16', 'both'),
+                    help="the learner's forward_precision (bf16: with target_precision='mixed'); both: the two "
+                         'forwards and update in each mode, side by side')
     args = ap.parse_args()
     if args.fold_trace:
         rec = fold_trace(args.fold_trace, args.updates, args.trace_shape)
         if args.record:
             with open(args.record) as fp:
                 whole = json.load(fp)
-            if whole.get('metric') == 'dqn_backward_bf16_us':       # one trace per shape, of the bf16 mode
+            if whole.get('metric') in ('dqn_backward_bf16_us', 'dqn_forward_bf16_us'):  # one trace per shape, of the bf16 mode
                 whole.setdefault('kernel_traces', {})[args.trace_shape] = rec
             else:
                 whole['kernel_trace'] = rec
@@ -206,22 +240,53 @@ def main():
     def spread(v):
         return {'median_us': sorted(v)[len(v) // 2], 'repeats_us': v}
 
-    def setup(shape, precision=None):
+    def setup(shape, precision=None, forward=None):
+        forward = forward or args.forward_precision
         h, w, c = SHAPES[shape]
         torch.manual_seed(0)
         policy, target = TorchDQN(h, w, c, 3).cuda(), TorchDQN(h, w, c, 3).cuda()
         target.load_state_dict(policy.state_dict())
         learner = DQNLearner(policy.state_dict(), h, w, c, num_actions=3,
-                             backward_precision=precision or args.backward_precision)
+                             backward_precision=precision or args.backward_precision, forward_precision=forward,
+                             target_precision='mixed' if forward == 'bf16' else 'fp32')
         return h, w, c, policy, target, learner, [batch(h, w, c, s) for s in range(4)]
 
+    if args.forward_precision == 'both' and args.backward_precision == 'both':
+        sys.exit('--forward-precision both compares the forwards under one --backward-precision: fp32 or bf16')
     if args.trace_loop:
-        if args.backward_precision == 'both':
-            sys.exit('--trace-loop traces one mode: --backward-precision fp32 or bf16')
+        if 'both' in (args.backward_precision, args.forward_precision):
+            sys.exit('--trace-loop traces one mode: --backward-precision and --forward-precision fp32 or bf16')
         h, w, c, _, _, learner, batches = setup(args.trace_shape)
         for i in range(args.trace_loop):
             learner.update(*batches[i % len(batches)])
         torch.cuda.synchronize()
+        return
+
+    if args.forward_precision == 'both':
+        rec = {'metric': 'dqn_forward_bf16_us', 'device': torch.cuda.get_device_name(0), 'batch': BATCH,
+               'launches': args.launches, 'warmup': args.warmup, 'repeats': args.repeats,
+               'backward_precision': args.backward_precision,
+               'timing': 'one HIP event pair per call, enqueued behind ~30 ms of filler work',
+               'yardstick': "the fp32-forward learner (forward_precision='fp32', target_precision='fp32') timed in "
+                            "the same process on the same batches; the bf16 one has target_precision='mixed'"}
+        for shape in args.shapes.split(','):
+            e = {}
+            for mode in ('fp32', 'bf16'):
+                h, w, c, _, _, learner, batches = setup(shape, forward=mode)
+                e[mode] = {'policy_forward': spread(medians_us(lambda b: learner(b[0]), batches)),
+                           'target_forward': spread(medians_us(lambda b: learner.target_q(b[3]), batches)),
+                           'update': spread(medians_us(lambda b: learner.update(*b), batches))}
+                del learner
+            e['obs_shape'] = [h, w, c]
+            e['forward_gemm_flops'] = sum(forward_gemm_flops(h, w, c).values())
+            for stage in ('policy_forward', 'target_forward', 'update'):
+                e['%s_bf16_over_fp32' % stage] = e['bf16'][stage]['median_us'] / e['fp32'][stage]['median_us']
+            rec[shape] = e
+        print(json.dumps(rec), flush=True)
+        out = args.out or FWD16_RECORD
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, 'w') as fp:
+            fp.write(json.dumps(rec, indent=1) + '\n')
         return
 
     if args.backward_precision == 'both':
