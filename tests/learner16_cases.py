@@ -1,13 +1,7 @@
-"""The float64 model of the bf16 backward (snake_dqn32_backward_bf16) and the
-cases of its tests (no GPU needed here), so that tests/test_learner_bf16_cpu.py
-proves exactly what tests/test_learner_bf16_gpu.py relies on.
-
-The model is the backward layer by layer in float64 with bf16 rounding,
-t.float().bfloat16().double(), at exactly the points include/snake_env.h names:
-both operands of the five weight-gradient GEMMs of the matrix cores (dY, and
-act(X) after it is formed) and of the four input-gradient GEMMs (dY and W).
-Masks come from the float64 forward; dX is kept unrounded between layers; bias
-gradients sum the unrounded dY; fc3's three stages are unrounded.
+"""The cases of the bf16 backward's tests (snake_dqn32_backward_bf16; no GPU
+needed here), so that tests/test_learner_bf16_cpu.py proves exactly what
+tests/test_learner_bf16_gpu.py relies on. The float64 model they run on, and
+the rounding points it states, are tests/learner_model.py's backward_model.
 
 Cases:
   existing    tests/learner_cases.py's probes: every staged operand is an integer
@@ -26,11 +20,7 @@ import math
 import torch
 
 import learner_cases as LC
-
-F = torch.nn.functional
-G = torch.nn.grad
-
-CONVS = ('conv1', 'conv2', 'conv3')
+import learner_model as M
 
 ROUNDING_KEYS = ((5, 5, 8, 3, 0, 70), (5, 5, 24, 5, 0, 70), (20, 20, 8, 3, 0, 5))
 ROUNDING_SCALE = 29.0
@@ -38,92 +28,11 @@ ROUNDING_SCALE = 29.0
 ROUNDED_DY = {ROUNDING_KEYS[0]: (1, 2, 3, 4, 5), ROUNDING_KEYS[1]: (1, 2, 3, 4, 5), ROUNDING_KEYS[2]: (1, 2, 3, 4)}
 
 
-def bf16(t):
-    """Round to nearest even to bf16, as a float64 tensor."""
-    return t.float().bfloat16().double()
-
-
-def exact(t):
-    return t
-
-
-def forward_pre(state, obs):
-    """The float64 forward: (x NCHW, the five pre-activations Y + b, conv ones NCHW)."""
-    s = {k: v.detach().double().cpu() for k, v in state.items()}
-    x = LC.input64(obs)
-    pre, t = [], x
-    for name in CONVS:
-        p = F.conv2d(t, s[name + '.weight'], s[name + '.bias'], padding=1)
-        pre.append(p)
-        t = F.relu(p)
-    t = t.reshape(t.size(0), -1)
-    for name in ('fc1', 'fc2'):
-        p = F.linear(t, s[name + '.weight'], s[name + '.bias'])
-        pre.append(p)
-        t = F.relu(p)
-    return x, pre
-
-
-def backward_model(state, obs, dq, rnd=bf16):
-    """(grads, staged, sum_bound). grads: reference names and layouts. staged:
-    every value a matrix-core GEMM stages, BEFORE rounding: 'x', 'c1', 'c2', 'c3',
-    'h1' (the activations), 'w:conv2', 'w:conv3', 'w:fc1', 'w:fc2' (the input
-    gradients' weights), 'dY1'..'dY5'. sum_bound: the largest sum of absolute
-    terms of any output element of any GEMM or bias sum of the chain, on the
-    operands as the chain stages them (rounded)."""
-    s = {k: v.detach().double().cpu() for k, v in state.items()}
-    x, pre = forward_pre(state, obs)
-    masks = [(p > 0).double() for p in pre]
-    c1, c2, c3, h1, h2 = (F.relu(p) for p in pre)
-    B = x.size(0)
-    # the observation as conv1's weight gradient stages it: the byte, or byte / 255 in fp32
-    xb = obs.cpu().permute(0, 3, 1, 2).float()
-    x_in = (xb / 255.0 if float(xb.max()) > 1.0 else xb).double()
-    dq = dq.double().cpu()
-    grads, staged, bound = {}, {'x': x_in, 'c1': c1, 'c2': c2, 'c3': c3, 'h1': h1}, [0.0]
-
-    def note(v):
-        bound[0] = max(bound[0], float(v.max()))
-
-    # fc3: unrounded
-    grads['fc3.weight'], grads['fc3.bias'] = dq.t() @ h2, dq.sum(0)
-    note(dq.abs().t() @ h2.abs())
-    note(dq.abs().sum(0))
-    dy = (dq @ s['fc3.weight']) * masks[4]
-    note(dq.abs() @ s['fc3.weight'].abs())
-    # fc2, fc1
-    c3f = c3.reshape(B, -1)
-    for name, act, mask, idx in (('fc2', h1, masks[3], 5), ('fc1', c3f, masks[2].reshape(B, -1), 4)):
-        staged['dY%d' % idx], staged['w:' + name] = dy, s[name + '.weight']
-        r_dy, r_act, r_w = rnd(dy), rnd(act), rnd(s[name + '.weight'])
-        grads[name + '.weight'], grads[name + '.bias'] = r_dy.t() @ r_act, dy.sum(0)
-        note(r_dy.abs().t() @ r_act.abs())
-        note(dy.abs().sum(0))
-        note(r_dy.abs() @ r_w.abs())
-        dy = (r_dy @ r_w) * mask
-    dy = dy.reshape(c3.shape)
-    # conv3, conv2, conv1
-    for name, act, mask, idx in (('conv3', c2, masks[1], 3), ('conv2', c1, masks[0], 2), ('conv1', x_in, None, 1)):
-        w = s[name + '.weight']
-        staged['dY%d' % idx] = dy
-        r_dy, r_act = rnd(dy), rnd(act)
-        grads[name + '.weight'] = G.conv2d_weight(r_act, w.shape, r_dy, padding=1)
-        grads[name + '.bias'] = dy.sum((0, 2, 3))
-        note(G.conv2d_weight(r_act.abs(), w.shape, r_dy.abs(), padding=1))
-        note(dy.abs().sum((0, 2, 3)))
-        if mask is not None:
-            staged['w:' + name] = w
-            r_w = rnd(w)
-            note(G.conv2d_input(act.shape, r_w.abs(), r_dy.abs(), padding=1))
-            dy = G.conv2d_input(act.shape, r_w, r_dy, padding=1) * mask
-    return grads, staged, bound[0]
-
-
 def ref_grads_bf16(state, obs, dq):
     """The float64 model of snake_dqn32_backward_bf16: the gradients of
     sum(dq * Q(obs)) with bf16 rounding at the header's rounding points;
     reference names and layouts, like learner_cases.ref_grads."""
-    return backward_model(state, obs, dq, bf16)[0]
+    return M.backward_model(state, obs, dq, M.bf16)[0]
 
 
 @functools.lru_cache(maxsize=None)
@@ -137,7 +46,7 @@ def rounding_case(key):
 # ---- the real-valued case ---------------------------------------------------------
 REAL_GEOM = (3, 4, 8, 3)        # h, w, c, A
 REAL_B = 6
-# The first seed from 0 at which mask_margin() >= MASK_MARGIN holds for the case
+# The first seed from 0 at which margin(..., exact) >= MASK_MARGIN holds for the case
 # and for its obs * 255 variant (tests/test_learner_bf16_cpu.py asserts it holds).
 REAL_SEED = 0
 # |Y + b| >= 2e-5 of the layer's max |Y + b|: twice the fp32 forward's documented
@@ -164,14 +73,10 @@ def real_case(seed=None, scaled=False):
     return state, obs.contiguous(), dq.contiguous()
 
 
-def mask_margin(state, obs):
-    """min over the five ReLU layers of min |Y + b| / max |Y + b| (float64)."""
-    _, pre = forward_pre(state, obs)
-    return min(float(p.abs().min() / p.abs().max()) for p in pre)
-
-
-def first_stable_seed(limit=200):
+def first_stable_seed(rnd, limit=200):
+    """The first seed at which every unit of the chain with that rounding (and of
+    its obs * 255 variant) is MASK_MARGIN of its layer's scale off its ReLU threshold."""
     for seed in range(limit):
-        if all(mask_margin(*real_case(seed, sc)[:2]) >= MASK_MARGIN for sc in (False, True)):
+        if all(M.margin(*real_case(seed, sc)[:2], rnd) >= MASK_MARGIN for sc in (False, True)):
             return seed
     raise AssertionError('no seed below %d keeps every unit off its ReLU threshold' % limit)

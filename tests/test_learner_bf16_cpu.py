@@ -2,13 +2,12 @@
 tests/test_learner_bf16_gpu.py's comparisons rest on.
 
 Existing probes: bf16 holds every staged GEMM operand exactly, so the model of
-tests/learner16_cases.py equals the autograd reference. Rounding cases (dq x 29):
+tests/learner_model.py equals the autograd reference. Rounding cases (dq x 29):
 all integers, every sum of absolute terms below 2^24, rounding does change
 operands and results. Real-valued case: no unit sits close enough to its ReLU
 threshold for the fp32 forward to mask it differently. And the new entry point
 is exported and validates its arguments like the fp32 one, before any launch."""
 import ctypes
-import os
 
 import pytest
 import torch
@@ -16,33 +15,24 @@ import torch
 import dqn_probe as P
 import learner16_cases as L16
 import learner_cases as LC
-
-
-@pytest.fixture(scope='module')
-def native():
-    from marlenv import _native
-    if not os.path.exists(_native.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return _native
-
+import learner_model as M
+from learner_gpu_util import key_ids, native, run_ids  # noqa: F401 (native is a fixture)
 
 ALL_RUNS = LC.gpu_backward_runs()
-RUN_IDS = ['%dx%dx%d-A%d-s%d-B%d' % (k[:5] + (b,)) for k, b in ALL_RUNS]
-KEY_IDS = ['%dx%dx%d-A%d-s%d-B%d' % k for k in L16.ROUNDING_KEYS]
+RUN_IDS, KEY_IDS = run_ids(ALL_RUNS), key_ids(L16.ROUNDING_KEYS)
 
 
 @pytest.mark.parametrize('key,B', ALL_RUNS, ids=RUN_IDS)
 def test_existing_probes_stage_only_bf16_values(key, B):
     case = LC.backward_case(key, B)
-    grads, staged, bound = L16.backward_model(case.state, case.obs, case.dq)
+    grads, staged, bound = M.backward_model(case.state, case.obs, case.dq)
     assert set(staged) == {'x', 'c1', 'c2', 'c3', 'h1', 'w:conv2', 'w:conv3', 'w:fc1', 'w:fc2',
                            'dY1', 'dY2', 'dY3', 'dY4', 'dY5'}
     top = {n: float(v.abs().max()) for n, v in staged.items()}
     print(top)
     for name, v in staged.items():
         assert torch.equal(v, v.round()) and top[name] < 256, name      # integers below 2^8: exact in bf16
-        assert torch.equal(L16.bf16(v), v), name
+        assert torch.equal(M.bf16(v), v), name
     for name in LC.PARAMS:
         assert torch.equal(grads[name], case.grads[name]), name
     assert bound < LC.SUM_LIMIT
@@ -52,7 +42,7 @@ def test_the_unrounded_model_is_the_autograd_reference():
     """backward_model with no rounding is ref_grads, also where rounding matters."""
     for key in L16.ROUNDING_KEYS[:2]:
         case, dq, _ = L16.rounding_case(key)
-        grads = L16.backward_model(case.state, case.obs, dq, L16.exact)[0]
+        grads = M.backward_model(case.state, case.obs, dq, M.exact)[0]
         ref = LC.ref_grads(case.state, case.obs, dq)
         for name in LC.PARAMS:
             assert torch.equal(grads[name], ref[name]), (key, name)
@@ -61,7 +51,7 @@ def test_the_unrounded_model_is_the_autograd_reference():
 @pytest.mark.parametrize('key', L16.ROUNDING_KEYS, ids=KEY_IDS)
 def test_rounding_cases_are_exact_and_do_round(key):
     case, dq, model = L16.rounding_case(key)
-    grads, staged, bound = L16.backward_model(case.state, case.obs, dq)
+    grads, staged, bound = M.backward_model(case.state, case.obs, dq)
     for name in LC.PARAMS:
         assert torch.equal(grads[name], model[name])
         assert torch.equal(model[name], model[name].round()), name
@@ -72,12 +62,12 @@ def test_rounding_cases_are_exact_and_do_round(key):
     assert bound < LC.SUM_LIMIT
     assert max(float(g.abs().max()) for g in model.values()) <= bound
     # rounding changes the dY buffers: of the float64 reference's chain (29 x the probe's) ...
-    _, exact_staged, _ = L16.backward_model(case.state, case.obs, dq, L16.exact)
-    changed = {i: int((L16.bf16(exact_staged['dY%d' % i]) != exact_staged['dY%d' % i]).sum()) for i in range(1, 6)}
+    _, exact_staged, _ = M.backward_model(case.state, case.obs, dq, M.exact)
+    changed = {i: int((M.bf16(exact_staged['dY%d' % i]) != exact_staged['dY%d' % i]).sum()) for i in range(1, 6)}
     # ... and of the model's chain. There dY3 is an exception by construction: the
     # probe's fc1 has one +-1 weight per column, so every dY3 entry is a copy of a
     # ROUNDED dY4 entry and is a bf16 value already.
-    own = {i: int((L16.bf16(staged['dY%d' % i]) != staged['dY%d' % i]).sum()) for i in range(1, 6)}
+    own = {i: int((M.bf16(staged['dY%d' % i]) != staged['dY%d' % i]).sum()) for i in range(1, 6)}
     print('unrepresentable entries: reference chain %s, model chain %s' % (changed, own))
     for i in L16.ROUNDED_DY[key]:
         assert changed[i] > 0, i
@@ -88,7 +78,7 @@ def test_rounding_cases_are_exact_and_do_round(key):
         assert [changed[i] for i in range(1, 6)] == [10744, 8549, 2181, 660, 69]
     # weights stay below 2^8: only dY is rounded here
     for name in ('x', 'c1', 'c2', 'c3', 'h1', 'w:conv2', 'w:conv3', 'w:fc1', 'w:fc2'):
-        assert torch.equal(L16.bf16(staged[name]), staged[name]), name
+        assert torch.equal(M.bf16(staged[name]), staged[name]), name
     # and the result is not 29 x the unrounded one
     for name in ('conv1.weight', 'conv2.weight', 'conv3.weight', 'fc1.weight'):
         assert not torch.equal(model[name], L16.ROUNDING_SCALE * case.grads[name]), name
@@ -108,11 +98,11 @@ def test_real_case_masks_are_stable(scaled):
     state, obs, dq = L16.real_case(scaled=scaled)
     assert tuple(obs.shape) == (6, 3, 4, 8) and tuple(dq.shape) == (6, 3)
     assert int(obs.max()) == (255 if scaled else 1)
-    margin = L16.mask_margin(state, obs)
+    margin = M.margin(state, obs, M.exact)
     print('min |Y + b| / max |Y + b| = %.3g' % margin)
     assert margin >= L16.MASK_MARGIN
     model, ref = L16.ref_grads_bf16(state, obs, dq), LC.ref_grads(state, obs, dq)
-    exact = L16.backward_model(state, obs, dq, L16.exact)[0]
+    exact = M.backward_model(state, obs, dq, M.exact)[0]
     for name in LC.PARAMS:
         assert model[name].shape == ref[name].shape
         scale = float(ref[name].abs().max())
@@ -127,7 +117,7 @@ def test_real_case_masks_are_stable(scaled):
 
 
 def test_real_seed_is_the_first_stable_one():
-    assert L16.first_stable_seed() == L16.REAL_SEED
+    assert L16.first_stable_seed(M.exact) == L16.REAL_SEED
 
 
 # ---- exports and validation ------------------------------------------------------

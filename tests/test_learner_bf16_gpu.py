@@ -4,7 +4,7 @@ dqn_train16_kernels.hip, snake_dqn32_backward_bf16).
 On the integer probes of tests/learner_cases.py bf16 holds every staged operand
 exactly, so the result must EQUAL the float64 autograd reference, as the fp32
 backward's does. On the rounding cases (dq x 29) it must EQUAL the float64 model
-of tests/learner16_cases.py, which rounds exactly where include/snake_env.h says
+of tests/learner_model.py, which rounds exactly where include/snake_env.h says
 the kernel rounds (tests/test_learner_bf16_cpu.py proves both preconditions).
 On real values it stays within a tolerance the model sets. update() in bf16 mode
 is bit-equal to its stages, reproducible, and checkpoints move between modes."""
@@ -14,16 +14,10 @@ import torch
 import dqn_probe as P
 import learner16_cases as L16
 import learner_cases as LC
+from learner_gpu_util import (DEV, check_checkpoints_move, check_update_equals_its_stages, key_ids, make_learner,
+                              run_ids)
 
 pytestmark = pytest.mark.gpu
-
-DEV = 'cuda:0'
-
-
-def make_learner(state, key, **kw):
-    from marlenv import DQNLearner
-    h, w, c, A = key[:4]
-    return DQNLearner(state, h, w, c, num_actions=A, device=DEV, **kw)
 
 
 def run_backward(state, key, obs, dq, precision='bf16'):
@@ -64,7 +58,7 @@ def localise(key, B, scale=1.0):
 RUNS = LC.gpu_backward_runs()
 
 
-@pytest.mark.parametrize('key,B', RUNS, ids=['%dx%dx%d-A%d-s%d-B%d' % (k[:5] + (b,)) for k, b in RUNS])
+@pytest.mark.parametrize('key,B', RUNS, ids=run_ids(RUNS))
 def test_bf16_backward_equals_float64_reference(key, B):
     case = LC.backward_case(key, B)
     q, got = run_backward(case.state, key, case.obs, case.dq)
@@ -73,7 +67,7 @@ def test_bf16_backward_equals_float64_reference(key, B):
     assert not wrong, '%s; %s' % (wrong, localise(key, B))
 
 
-@pytest.mark.parametrize('key', L16.ROUNDING_KEYS, ids=['%dx%dx%d-A%d-s%d-B%d' % k for k in L16.ROUNDING_KEYS])
+@pytest.mark.parametrize('key', L16.ROUNDING_KEYS, ids=key_ids(L16.ROUNDING_KEYS))
 def test_bf16_backward_equals_the_rounding_model(key):
     case, dq, model = L16.rounding_case(key)
     _, got = run_backward(case.state, key, case.obs, dq)
@@ -118,77 +112,12 @@ def test_bf16_backward_real_values_within_the_model_tolerance(scaled):
 
 
 # ---- composition, determinism, checkpoints -----------------------------------------
-def probe_batch(B=64):
-    g = P._gen(B, 31337)
-    state, next_state = P.probe_obs(B, 5, 5, 8, 21), P.probe_obs(B, 5, 5, 8, 22)
-    action = torch.randint(0, 3, (B,), generator=g)
-    reward = torch.randint(-2, 3, (B,), generator=g).float()
-    done = (torch.rand(B, generator=g) < 0.25).float()
-    return tuple(t.to(DEV) for t in (state, action, reward, next_state, done))
-
-
-KEY5 = (5, 5, 8, 3)
-
-
-def snapshot(learner):
-    return [learner._param.clone(), learner._m.clone(), learner._v.clone(), learner._target.clone()]
-
-
-def same(a, b):
-    return all(torch.equal(x, y) for x, y in zip(a, b))
-
-
 def test_bf16_update_equals_its_stages_and_is_reproducible():
-    state, _ = LC.descent_batch()                                     # real-valued: rounding matters from step 1
-    batch = probe_batch()
-    s, a, r, ns, d = batch
-    kw = dict(backward_precision='bf16')
-    whole, by_hand, fp32 = make_learner(state, KEY5, **kw), make_learner(state, KEY5, **kw), make_learner(state, KEY5)
-    losses, hand_losses, ckpt = [], [], None
-    for i in range(3):
-        losses.append(whole.update(*batch))
-        fp32.update(*batch)
-        nq = by_hand.target_q(ns)
-        q = by_hand(s)
-        loss, dq = by_hand.td_loss(q, a, r, d, nq)
-        by_hand.backward(s, dq)
-        by_hand.apply()
-        hand_losses.append(loss)
-        if i == 0:
-            ckpt = whole.checkpoint()
-    assert whole.step == by_hand.step == 3
-    assert same(snapshot(whole), snapshot(by_hand))
-    assert all(torch.equal(x, y) for x, y in zip(losses, hand_losses))
-    assert not torch.equal(whole._param, fp32._param)                  # the bf16 backward is another computation
-    assert torch.equal(whole._target, fp32._target)
-    # updates 2 and 3 again, twice, from the checkpoint after update 1 (a fresh learner each time)
-    for _ in range(2):
-        again = make_learner(P.probe_net(5, 5, 8, 3, 1), KEY5, **kw)
-        again.load_checkpoint(ckpt)
-        assert again.step == 1
-        l2, l3 = again.update(*batch), again.update(*batch)
-        assert same(snapshot(again), snapshot(whole))
-        assert torch.equal(l2, losses[1]) and torch.equal(l3, losses[2])
-    assert float(whole.grad_norm) > 0
+    check_update_equals_its_stages(dict(backward_precision='bf16'))
 
 
 def test_checkpoints_move_between_the_modes():
-    state, _ = LC.descent_batch()
-    batch = probe_batch()
-    for first, second in (('bf16', 'fp32'), ('fp32', 'bf16')):
-        a = make_learner(state, KEY5, backward_precision=first)
-        a.update(*batch)
-        ckpt = a.checkpoint()
-        b = make_learner(P.probe_net(5, 5, 8, 3, 1), KEY5, backward_precision=second)
-        b.load_checkpoint(ckpt)
-        assert b.backward_precision == second and b.step == 1
-        assert same(snapshot(b), snapshot(a))
-        # from the same state, the loaded learner continues as one of its own mode does
-        c = make_learner(P.probe_net(5, 5, 8, 3, 1), KEY5, backward_precision=second)
-        c.load_checkpoint(ckpt)
-        assert torch.equal(b.update(*batch), c.update(*batch)) and same(snapshot(b), snapshot(c))
-        a.update(*batch)
-        assert not torch.equal(a._param, b._param)                     # and not as the other mode
+    check_checkpoints_move('backward_precision')
 
 
 def test_default_mode_is_the_fp32_backward():

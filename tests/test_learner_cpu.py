@@ -5,28 +5,18 @@ wrong weight), the dyadic TD case is exact in fp32, torch's own Adam lowers the
 loss on the descent batch, and the library's host-side plan calls return the
 documented sizes and messages."""
 import ctypes
-import os
 
 import pytest
 import torch
 
 import dqn_probe as P
 import learner_cases as LC
-
-
-@pytest.fixture(scope='module')
-def native():
-    from marlenv import _native
-    if not os.path.exists(_native.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return _native
-
+from learner_gpu_util import native, run_ids  # noqa: F401 (native is a fixture)
 
 ALL_RUNS = LC.gpu_backward_runs()
 
 
-@pytest.mark.parametrize('key,B', ALL_RUNS, ids=['%dx%dx%d-A%d-s%d-B%d' % (k[:5] + (b,)) for k, b in ALL_RUNS])
+@pytest.mark.parametrize('key,B', ALL_RUNS, ids=run_ids(ALL_RUNS))
 def test_probe_gradients_are_exact_integers(key, B):
     case = LC.backward_case(key, B)
     for name, g in case.grads.items():

@@ -2,7 +2,7 @@
 tests/test_learner_fwd16_gpu.py's comparisons rest on.
 
 Probes: bf16 holds every staged GEMM operand exactly, so the model of
-tests/learner_fwd16_cases.py equals dqn_probe.ref64 and the gradients that
+tests/learner_model.py equals dqn_probe.ref64 and the gradients that
 continue from it equal the autograd reference. Rounding cases (conv1 x 61): all
 integers, every sum of absolute terms below 2^24, rounding does change operands
 and results. Real-valued case: no unit of the model's chain sits close to its
@@ -10,7 +10,6 @@ ReLU threshold. The split-K rule, restated, puts the GPU cases on both sides of
 it. And the new entry points are exported and validate their arguments like the
 fp32 ones, before any launch."""
 import ctypes
-import os
 
 import pytest
 import torch
@@ -19,66 +18,58 @@ import dqn_probe as P
 import learner16_cases as L16
 import learner_cases as LC
 import learner_fwd16_cases as FC
-
-
-@pytest.fixture(scope='module')
-def native():
-    from marlenv import _native
-    if not os.path.exists(_native.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return _native
-
+import learner_model as M
+from learner_gpu_util import key_ids, native, run_ids  # noqa: F401 (native is a fixture)
 
 ALL_RUNS = LC.gpu_backward_runs()
-RUN_IDS = ['%dx%dx%d-A%d-s%d-B%d' % (k[:5] + (b,)) for k, b in ALL_RUNS]
-KEY_IDS = ['%dx%dx%d-A%d-s%d-B%d' % k for k in FC.ROUNDING_KEYS]
-
-
-def nchw(y):
-    return y.permute(0, 3, 1, 2) if y.dim() == 4 else y
+RUN_IDS, KEY_IDS = run_ids(ALL_RUNS), key_ids(FC.ROUNDING_KEYS)
 
 
 @pytest.mark.parametrize('key,B', ALL_RUNS, ids=RUN_IDS)
 def test_probes_stage_only_bf16_values(key, B):
     case = LC.backward_case(key, B)
-    model = FC.forward_model(case.state, case.obs)
+    model = M.forward_model(case.state, case.obs)
     feat, q, acts = P.ref64(case.state, case.obs)
     assert set(model.staged) == set(P.ROUNDED)
     for name, v in model.staged.items():
         assert torch.equal(v, v.round()) and float(v.abs().max()) < 256, name     # integers below 2^8: exact in bf16
-        assert torch.equal(L16.bf16(v), v), name
+        assert torch.equal(M.bf16(v), v), name
     for name in P.LAYERS:
         w = case.state[name + '.weight'].double()
-        assert torch.equal(L16.bf16(w), w), name
+        assert torch.equal(M.bf16(w), w), name
     for i, dst in enumerate(('c1', 'c2', 'c3', 'h1', 'h2')):
         assert torch.equal(torch.relu(model.pre[i]), acts[dst]), dst
     assert torch.equal(model.feat, feat) and torch.equal(model.q, q)
     assert torch.equal(q, P.probe(*key).q[:B])
     assert model.bound < LC.SUM_LIMIT
     for rnd in FC.BACKWARD_RND.values():
-        grads, bound = FC.backward_from(case.state, case.obs, model.pre, case.dq, rnd)
+        grads, _, bound = M.backward_model(case.state, case.obs, case.dq, rnd, pre=model.pre)
         assert bound < LC.SUM_LIMIT
         for name in LC.PARAMS:
             assert torch.equal(grads[name], case.grads[name]), name
 
 
 def test_the_backward_chain_is_learner16_cases_chain():
-    """backward_from on the float64 forward's pre-activations is learner16_cases.backward_model."""
-    case, dq, model = L16.rounding_case(L16.ROUNDING_KEYS[0])
-    pre = L16.forward_pre(case.state, case.obs)[1]
-    grads, bound = FC.backward_from(case.state, case.obs, pre, dq)
-    assert bound == L16.backward_model(case.state, case.obs, dq)[2]
+    """backward_model's default start is the unrounded forward_model's pre-activations,
+    those are dqn_probe.ref64's, and learner16_cases' stored gradients are that chain's."""
+    case, dq, stored = L16.rounding_case(L16.ROUNDING_KEYS[0])
+    pre = M.forward_model(case.state, case.obs, M.exact).pre
+    grads, _, bound = M.backward_model(case.state, case.obs, dq)
+    given, _, given_bound = M.backward_model(case.state, case.obs, dq, pre=pre)
+    assert bound == given_bound
+    acts = P.ref64(case.state, case.obs)[2]
+    for p, dst in zip(pre, ('c1', 'c2', 'c3', 'h1', 'h2')):
+        assert torch.equal(torch.relu(p), acts[dst]) and torch.equal(p > 0, acts[dst] > 0), dst
     for name in LC.PARAMS:
-        assert torch.equal(grads[name], model[name]), name
+        assert torch.equal(grads[name], given[name]) and torch.equal(grads[name], stored[name]), name
 
 
 def test_bytes_0_255_case_is_the_0_1_case():
     case = LC.backward_case(FC.BYTES_KEY)
     obs = case.obs * 255
     assert int(obs.max()) == 255
-    assert torch.equal(FC.staged_input(obs), FC.staged_input(case.obs))         # 255 / 255 is 1.0f
-    a, b = FC.forward_model(case.state, obs), FC.forward_model(case.state, case.obs)
+    assert torch.equal(M.staged_input(obs), M.staged_input(case.obs))         # 255 / 255 is 1.0f
+    a, b = M.forward_model(case.state, obs), M.forward_model(case.state, case.obs)
     assert torch.equal(a.q, b.q) and all(torch.equal(a.Y[n], b.Y[n]) for n in FC.YS)
 
 
@@ -105,14 +96,14 @@ def test_rounding_cases_are_exact_and_do_round(key):
     feat, q, _ = P.ref64(c.state, c.obs)
     assert torch.equal(unrounded.q, q) and torch.equal(unrounded.feat, feat)
     # rounding changes entries of c1, c2, c3 and h1 (x and the weights are bf16 values) ...
-    changed = {n: int((L16.bf16(v) != v).sum()) for n, v in model.staged.items()}
+    changed = {n: int((M.bf16(v) != v).sum()) for n, v in model.staged.items()}
     print('unrepresentable staged entries: %s' % changed)
     assert changed['x'] == 0
     for name in ('c1', 'c2', 'c3', 'h1'):
         assert changed[name] > 0, name
     for name in P.LAYERS:
         w = c.state[name + '.weight'].double()
-        assert torch.equal(L16.bf16(w), w), name
+        assert torch.equal(M.bf16(w), w), name
     # ... so Y1 is the unrounded one, and Y2..Y5 and Q are not
     assert torch.equal(model.Y['Y1'], unrounded.Y['Y1'])
     for name in FC.YS[1:]:
@@ -129,18 +120,18 @@ def test_rounding_cases_are_exact_and_do_round(key):
 def test_scale_29_would_not_round_conv1s_output():
     """Why the scale is 61: at learner16_cases' 29 every c1 entry stays a bf16 value."""
     case = LC.backward_case(FC.ROUNDING_KEYS[0])
-    c1 = FC.forward_model(FC.scaled_state(case.state, 29.0), case.obs).staged['c1']
-    assert torch.equal(L16.bf16(c1), c1)
+    c1 = M.forward_model(FC.scaled_state(case.state, 29.0), case.obs).staged['c1']
+    assert torch.equal(M.bf16(c1), c1)
 
 
 @pytest.mark.parametrize('scaled', [False, True], ids=['bytes-0-1', 'bytes-0-255'])
 def test_real_case_is_stable_on_the_models_chain(scaled):
     state, obs, dq = FC.real_case(scaled)
     assert tuple(obs.shape) == (6, 3, 4, 8) and int(obs.max()) == (255 if scaled else 1)
-    margin = FC.model_margin(state, obs)
+    margin = M.margin(state, obs, M.bf16)
     print('model chain: min |Y + b| / max |Y + b| = %.3g' % margin)
     assert margin >= L16.MASK_MARGIN
-    model, ref = FC.forward_model(state, obs), FC.reference_y(state, obs)
+    model, ref = M.forward_model(state, obs), FC.reference_y(state, obs)
     for name in FC.YS:
         rel = float((model.Y[name] - ref[name]).norm() / ref[name].norm())
         print('%s |model - ref64| / |ref64| = %.3g' % (name, rel))
@@ -150,7 +141,7 @@ def test_real_case_is_stable_on_the_models_chain(scaled):
 
 
 def test_real_seed_is_the_first_stable_one():
-    assert FC.first_stable_seed() == FC.REAL_SEED
+    assert L16.first_stable_seed(M.bf16) == FC.REAL_SEED
 
 
 # ---- the split-K rule ------------------------------------------------------------------

@@ -6,7 +6,7 @@ On the integer probes of tests/learner_cases.py bf16 holds every staged operand
 exactly, so Y1..Y5, the features and Q must EQUAL dqn_probe.ref64 and the
 gradients of either backward the autograd reference. On the rounding cases
 (conv1 x 61) everything must EQUAL the float64 model of
-tests/learner_fwd16_cases.py, which rounds exactly where include/snake_env.h
+tests/learner_model.py, which rounds exactly where include/snake_env.h
 says the kernel rounds (tests/test_learner_fwd16_cpu.py proves the
 preconditions). On real values it stays within a tolerance the model sets. Rows
 do not depend on their batch; update() is bit-equal to its stages, reproducible,
@@ -18,17 +18,13 @@ import dqn_probe as P
 import learner16_cases as L16
 import learner_cases as LC
 import learner_fwd16_cases as FC
+import learner_model as M
+from learner_gpu_util import (DEV, KEY5, check_checkpoints_move, check_update_equals_its_stages, key_ids,
+                              make_learner, run_ids)
 
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda:0'
 ALL16 = dict(forward_precision='bf16', backward_precision='bf16', target_precision='mixed')
-
-
-def make_learner(state, key, **kw):
-    from marlenv import DQNLearner
-    h, w, c, A = key[:4]
-    return DQNLearner(state, h, w, c, num_actions=A, device=DEV, **kw)
 
 
 class Run:
@@ -78,7 +74,7 @@ def localise(key, B, scale=1.0):
         if scale != 1.0:
             state = FC.scaled_state(state, scale)
         obs = P.probe_obs(key[5], h, w, c, seed)[:B].contiguous()
-        model = FC.forward_model(state, obs)
+        model = M.forward_model(state, obs)
         wrong = wrong_tensors(Run(state, key, obs), model.Y, model.feat, model.q)
         if wrong:
             bad.append('%s alone: %s' % (layer, wrong))
@@ -88,7 +84,7 @@ def localise(key, B, scale=1.0):
 RUNS = LC.gpu_backward_runs()
 
 
-@pytest.mark.parametrize('key,B', RUNS, ids=['%dx%dx%d-A%d-s%d-B%d' % (k[:5] + (b,)) for k, b in RUNS])
+@pytest.mark.parametrize('key,B', RUNS, ids=run_ids(RUNS))
 def test_bf16_forward_equals_float64_reference(key, B):
     case = LC.backward_case(key, B)
     feat, q, _ = P.ref64(case.state, case.obs)
@@ -113,7 +109,7 @@ def test_bytes_0_255_take_the_flag_path_exactly():
             assert torch.equal(scaled.grads[mode][name], ones.grads[mode][name]), (mode, name)
 
 
-@pytest.mark.parametrize('key', FC.ROUNDING_KEYS, ids=['%dx%dx%d-A%d-s%d-B%d' % k for k in FC.ROUNDING_KEYS])
+@pytest.mark.parametrize('key', FC.ROUNDING_KEYS, ids=key_ids(FC.ROUNDING_KEYS))
 def test_bf16_forward_equals_the_rounding_model(key):
     c = FC.rounding_case(key)
     run = Run(c.state, key, c.obs, c.dq)
@@ -140,12 +136,12 @@ def test_bf16_forward_real_values_within_the_model_tolerance(scaled):
     layer's scale away from its threshold."""
     state, obs, dq = FC.real_case(scaled)
     key = L16.REAL_GEOM
-    model, ref_y = FC.forward_model(state, obs), FC.reference_y(state, obs)
+    model, ref_y = M.forward_model(state, obs), FC.reference_y(state, obs)
     q64, g64 = P.ref64(state, obs)[1], LC.ref_grads(state, obs, dq)
     run, run32 = Run(state, key, obs, dq), Run(state, key, obs, dq, forward='fp32')
     rows = [(n, run.Y[n], run32.Y[n], model.Y[n], ref_y[n]) for n in FC.YS] + [('Q', run.q, run32.q, model.q, q64)]
     for mode, rnd in FC.BACKWARD_RND.items():
-        grads = FC.backward_from(state, obs, model.pre, dq, rnd)[0]
+        grads = M.backward_model(state, obs, dq, rnd, pre=model.pre)[0]
         rows += [('%s/%s' % (n, mode), run.grads[mode][n], run32.grads[mode][n], grads[n], g64[n]) for n in LC.PARAMS]
     failed = []
     for name, got, got32, mod, ref in rows:
@@ -177,79 +173,12 @@ def test_rows_do_not_depend_on_their_batch():
 
 
 # ---- composition, determinism, checkpoints -----------------------------------------
-def probe_batch(B=64):
-    g = P._gen(B, 31337)
-    state, next_state = P.probe_obs(B, 5, 5, 8, 21), P.probe_obs(B, 5, 5, 8, 22)
-    action = torch.randint(0, 3, (B,), generator=g)
-    reward = torch.randint(-2, 3, (B,), generator=g).float()
-    done = (torch.rand(B, generator=g) < 0.25).float()
-    return tuple(t.to(DEV) for t in (state, action, reward, next_state, done))
-
-
-KEY5 = (5, 5, 8, 3)
-
-
-def snapshot(learner):
-    return [learner._param.clone(), learner._m.clone(), learner._v.clone(), learner._target.clone()]
-
-
-def same(a, b):
-    return all(torch.equal(x, y) for x, y in zip(a, b))
-
-
 def test_bf16_update_equals_its_stages_and_is_reproducible():
-    state, _ = LC.descent_batch()                                     # real-valued: rounding matters from step 1
-    batch = probe_batch()
-    s, a, r, ns, d = batch
-    whole, by_hand, fp32 = make_learner(state, KEY5, **ALL16), make_learner(state, KEY5, **ALL16), make_learner(state, KEY5)
-    losses, hand_losses, ckpt = [], [], None
-    for i in range(3):
-        losses.append(whole.update(*batch))
-        fp32.update(*batch)
-        nq = by_hand.target_q(ns)
-        q = by_hand(s)
-        loss, dq = by_hand.td_loss(q, a, r, d, nq)
-        by_hand.backward(s, dq)
-        by_hand.apply()
-        hand_losses.append(loss)
-        if i == 0:
-            ckpt = whole.checkpoint()
-            assert not torch.equal(whole._param, fp32._param)          # after one step already
-    assert whole.step == by_hand.step == 3
-    assert same(snapshot(whole), snapshot(by_hand))
-    assert all(torch.equal(x, y) for x, y in zip(losses, hand_losses))
-    assert not torch.equal(whole._param, fp32._param)
-    assert torch.equal(whole._target, fp32._target)
-    # updates 2 and 3 again, twice, from the checkpoint after update 1 (a fresh learner each time)
-    for _ in range(2):
-        again = make_learner(P.probe_net(5, 5, 8, 3, 1), KEY5, **ALL16)
-        again.load_checkpoint(ckpt)
-        assert again.step == 1
-        l2, l3 = again.update(*batch), again.update(*batch)
-        assert same(snapshot(again), snapshot(whole))
-        assert torch.equal(l2, losses[1]) and torch.equal(l3, losses[2])
-    assert float(whole.grad_norm) > 0
+    check_update_equals_its_stages(ALL16, differs_after_first_step=True)
 
 
 def test_checkpoints_move_between_the_forward_modes():
-    state, _ = LC.descent_batch()
-    batch = probe_batch()
-    for first, second in (('bf16', 'fp32'), ('fp32', 'bf16')):
-        a = make_learner(state, KEY5, forward_precision=first)
-        a.update(*batch)
-        ckpt = a.checkpoint()
-        b = make_learner(P.probe_net(5, 5, 8, 3, 1), KEY5, forward_precision=second)
-        b.load_checkpoint(ckpt)
-        assert b.forward_precision == second and b.step == 1
-        with pytest.raises(ValueError, match='policy forward'):
-            b.pre_activations()
-        assert same(snapshot(b), snapshot(a))
-        # from the same state, the loaded learner continues as one of its own mode does
-        c = make_learner(P.probe_net(5, 5, 8, 3, 1), KEY5, forward_precision=second)
-        c.load_checkpoint(ckpt)
-        assert torch.equal(b.update(*batch), c.update(*batch)) and same(snapshot(b), snapshot(c))
-        a.update(*batch)
-        assert not torch.equal(a._param, b._param)                     # and not as the other mode
+    check_checkpoints_move('forward_precision')
 
 
 def test_mixed_target_is_the_bf16_policy_forward_after_a_sync():

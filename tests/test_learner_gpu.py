@@ -14,16 +14,9 @@ import torch
 
 import dqn_probe as P
 import learner_cases as LC
+from learner_gpu_util import DEV, KEY5, make_learner, probe_batch, run_ids, same, snapshot
 
 pytestmark = pytest.mark.gpu
-
-DEV = 'cuda:0'
-
-
-def make_learner(state, key, **kw):
-    from marlenv import DQNLearner
-    h, w, c, A = key[:4]
-    return DQNLearner(state, h, w, c, num_actions=A, device=DEV, **kw)
 
 
 def run_backward(state, key, obs, dq):
@@ -52,7 +45,7 @@ def localise(key, B):
 RUNS = LC.gpu_backward_runs()
 
 
-@pytest.mark.parametrize('key,B', RUNS, ids=['%dx%dx%d-A%d-s%d-B%d' % (k[:5] + (b,)) for k, b in RUNS])
+@pytest.mark.parametrize('key,B', RUNS, ids=run_ids(RUNS))
 def test_backward_equals_float64_reference(key, B):
     case = LC.backward_case(key, B)
     q, got = run_backward(case.state, key, case.obs, case.dq)
@@ -221,27 +214,9 @@ def test_adam_step_within_the_derived_bound(scale, step):
 
 
 # ---- composition and determinism -------------------------------------------------
-def probe_batch(B=64):
-    g = P._gen(B, 31337)
-    state, next_state = P.probe_obs(B, 5, 5, 8, 21), P.probe_obs(B, 5, 5, 8, 22)
-    action = torch.randint(0, 3, (B,), generator=g)
-    reward = torch.randint(-2, 3, (B,), generator=g).float()
-    done = (torch.rand(B, generator=g) < 0.25).float()
-    return tuple(t.to(DEV) for t in (state, action, reward, next_state, done))
-
-
-KEY5 = (5, 5, 8, 3)
-
-
-def snapshot(learner):
-    return [learner._param.clone(), learner._m.clone(), learner._v.clone(), learner._target.clone()]
-
-
-def same(a, b):
-    return all(torch.equal(x, y) for x, y in zip(a, b))
-
-
 def test_update_equals_its_stages_and_is_reproducible():
+    """On the integer probe net, so not learner_gpu_util.check_update_equals_its_stages
+    (a real-valued net against its fp32 twin)."""
     state = P.probe_net(5, 5, 8, 3, 0)
     batch = probe_batch()
     s, a, r, ns, d = batch
