@@ -284,10 +284,28 @@ int snake_debug_set(const char *name, long long value);
  * (train_dqn.py:104-151 DQN.forward / forward_features, train_ga.py:60-100),
  * conv1 c->32, conv2 32->64, conv3 64->64 (3x3, pad 1, ReLU), NCHW flatten,
  * fc1 64hw->256, fc2 256->128 (ReLU), fc3 128->A, on the bf16 matrix cores with
- * fp32 accumulation (weights and activations rounded to bf16 between layers).
- * obs: uint8 [B][h][w][c] (the env's NHWC per-snake observations, 0/1 values:
- * the reference's /255 branch is not taken). h = w = 2*vision_range+1 with
- * vision_range in [1, 5], c = 8*frame_stack <= 32, A <= 4. */
+ * fp32 accumulation. The five GEMMs conv1, conv2, conv3, fc1 and fc2 run on
+ * v_mfma_f32_16x16x32_bf16: Y[m][n] = sum_k act(X)[m][k] * W[n][k] on bf16
+ * operands, products exact, sums fp32. The rounding points are those of
+ * snake_dqn32_forward_bf16 below; only the place differs (a value is rounded
+ * as it is stored, not as it is staged):
+ *   rounded      relu(Y + b) of conv1, conv2, conv3 and fc1, formed in fp32 and
+ *                rounded to bf16, to nearest even, as it is stored (in LDS, or
+ *                conv3's in act_scratch); the input byte becomes a bf16 value
+ *                (exact); the weights are bf16 already, rounded to nearest even
+ *                by the pack (snake_dqn_pack32)
+ *   not rounded  the biases (fp32); the fp32 accumulators; relu(fc2 + b) =
+ *                feat_out, fp32; fc3, in fp32 on those fp32 features and fp32
+ *                weights
+ *   input bytes  a byte is read at its value 0..255: the reference's /255
+ *                branch does not exist here, the functions are for the env's
+ *                0/1 observations
+ * tests/test_dqn_round_gpu.py holds both functions to a float64 model of
+ * exactly these points, bit for bit (tests/learner_model.py, the model of
+ * snake_dqn32_forward_bf16 too; cases in tests/dqn_round_cases.py).
+ * obs: uint8 [B][h][w][c] (the env's NHWC per-snake observations). h = w =
+ * 2*vision_range+1 with vision_range in [1, 5], c = 8*frame_stack <= 32,
+ * A <= 4. */
 typedef struct {
     int32_t height, width, channels, num_actions;
     int32_t conv_waves;     /* waves per observation in the conv kernel: 1, 2, 4; 0 = default (4,

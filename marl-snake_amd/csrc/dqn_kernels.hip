@@ -28,7 +28,11 @@
 //               or 16 waves per observation, a loop over the row tiles; same
 //               scratch layout, same k_dqn_fc (snake_dqn_map_forward).
 // Accumulation is fp32 everywhere; inputs and weights of the matrix products
-// are bf16 (tolerance against the fp32 reference: tests/test_dqn.py).
+// are bf16 (tolerance against the fp32 reference: tests/test_dqn.py). The
+// three epilogues that store relu(Y + b) of conv1, conv2, conv3 and fc1 round
+// it with bf16_bits(), to nearest even; nothing else is rounded (the rounding
+// points are in include/snake_env.h, held bit for bit by
+// tests/test_dqn_round_gpu.py against the float64 model of tests/learner_model.py).
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>

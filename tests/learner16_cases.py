@@ -54,10 +54,10 @@ REAL_SEED = 0
 MASK_MARGIN = 2e-5
 
 
-def real_case(seed=None, scaled=False):
+def real_case(seed=None, scaled=False, geom=REAL_GEOM):
     """(state, obs, dq): weights uniform in +-1/sqrt(fan_in), Bernoulli bytes
     (times 255 with scaled: the /255 branch), dq normal / B."""
-    h, w, c, A = REAL_GEOM
+    h, w, c, A = geom
     g = torch.Generator().manual_seed(REAL_SEED if seed is None else seed)
     shapes = (('conv1', (32, c, 3, 3)), ('conv2', (64, 32, 3, 3)), ('conv3', (64, 64, 3, 3)),
               ('fc1', (256, 64 * h * w)), ('fc2', (128, 256)), ('fc3', (A, 128)))

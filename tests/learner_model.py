@@ -11,7 +11,10 @@ snake_dqn32_backward_bf16); rnd=exact rounds nowhere, the fp32 kernels.
 Forward: act(X) and W of the five GEMMs conv1, conv2, conv3, fc1, fc2, and
 nowhere else: act(X) is the byte (or byte / 255 in fp32 when the batch holds a
 value > 1) or relu(Y_prev + b_prev); Y as stored, the biases, fc3 and the
-features are not rounded.
+features are not rounded. The fused bf16 forward (dqn_kernels.hip: snake_dqn_forward,
+snake_dqn_map_forward) rounds at the same points, as it stores relu(Y + b), and
+reads a byte at its value (forward_model's x = byte_input(obs));
+tests/dqn_round_cases.py holds its cases.
 
 Backward: both operands of the five weight-gradient GEMMs (dY, and act(X) after
 it is formed) and of the four input-gradient GEMMs (dY and W). Masks and act(X)
@@ -56,11 +59,19 @@ class Forward:
     of any of the six GEMMs, on the operands as staged."""
 
 
-def forward_model(state, obs, rnd=bf16):
+def byte_input(obs):
+    """conv1's act(X) of the fused bf16 forward (snake_dqn_forward,
+    snake_dqn_map_forward), which has no / 255 branch: the byte's value; NCHW float64."""
+    return obs.cpu().permute(0, 3, 1, 2).double()
+
+
+def forward_model(state, obs, rnd=bf16, x=None):
+    """x: conv1's act(X) where it is not staged_input(obs) (byte_input(obs) for the
+    fused bf16 forward on bytes above 1)."""
     s = {k: v.detach().double().cpu() for k, v in state.items()}
     out = Forward()
     out.Y, out.pre, out.staged, out.bound = {}, [], {}, 0.0
-    t = staged_input(obs)
+    t = staged_input(obs) if x is None else x.double().cpu()
     for i, (name, act_name) in enumerate(zip(P.LAYERS, P.ROUNDED)):
         w, b = s[name + '.weight'], s[name + '.bias']
         if name == 'fc1':
