@@ -27,6 +27,12 @@
 #ifndef SNAKE_TBL_EPW           // envs per one-wave table-encode wave
 #define SNAKE_TBL_EPW 4
 #endif
+#ifndef SNAKE_BG_TRIES_SMALL    // k_spawn: attempts per job on small background boards
+#define SNAKE_BG_TRIES_SMALL 2
+#endif
+#ifndef SNAKE_ENC_WPB           // k_post: table-encode waves per workgroup, at most
+#define SNAKE_ENC_WPB kEncWpbMax
+#endif
 
 namespace snake {
 
@@ -46,8 +52,6 @@ int launched(const char *what)
     if (err != hipSuccess) { set_error("%s launch failed: %s", what, hipGetErrorString(err)); return SNAKE_E_LAUNCH; }
     return SNAKE_OK;
 }
-
-static int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 static int pow2_at_least(int x)
 {
@@ -293,12 +297,11 @@ static int spawn_thr_of(const snake_cfg *c)
 // 0.0495 -> 0.0539, cfg4 0.0580 -> 0.0672, cfg3 0.0838 -> 0.0887.
 static bool bg_of(const snake_cfg *c, int64_t n_cand, int64_t N)
 {
-    const int64_t oh = c->vision_range ? 2 * c->vision_range + 1 : c->height;
-    const int64_t ow = c->vision_range ? 2 * c->vision_range + 1 : c->width;
+    const int64_t oh = obs_window(c->vision_range, c->height), ow = obs_window(c->vision_range, c->width);
     const int64_t obs = N * c->num_snakes * oh * ow * 8 * c->frame_stack;
     const bool small = N <= 8192 && obs <= ((int64_t)64 << 20);
     const bool want = c->spawn_background != 0 ? c->spawn_background > 0 : (n_cand > 8192 || small);
-    return want && spawn_thr_of(c) >= 0 && 2 * (n_cand + kWave) <= kJarrLdsMax;
+    return want && spawn_thr_of(c) >= 0 && draw_record_fits(n_cand);
 }
 
 // Lean-encode geometry (snake_kernels.hip encode_lean): the frames copied into a
@@ -319,18 +322,17 @@ static LeanGeom lean_geom(const snake_cfg *c)
 {
     LeanGeom g;
     const int vr = c->vision_range, fs = c->frame_stack, H = c->height, W = c->width, S = c->num_snakes;
-    const int oh = vr ? 2 * vr + 1 : H, ow = vr ? 2 * vr + 1 : W;
+    const int oh = obs_window(vr, H), ow = obs_window(vr, W);
     const int64_t units = (int64_t)S * oh * ow * fs;
     g.lp = vr ? (int)round_up(vr, 4) : 0;
     g.pw = vr ? (int)round_up(W + g.lp + vr, 4) : W;
     g.pframe = (int)round_up((int64_t)(H + 2 * vr) * g.pw, 16);
     g.ups = oh * ow * fs;
     g.rowl = ow * fs;
-    auto mag = [](uint64_t d) { return (uint32_t)(((1ull << 32) + d - 1) / d); };
     g.mag_ups = mag(g.ups); g.mag_rowl = mag(g.rowl); g.mag_fs = mag(fs);
     g.mag_wpr = mag(std::max(1, W / 4));
     g.lds_lean_bytes = (int)round_up((int64_t)fs * g.pframe, 16) + 4 * fs * kMaxSnakes;
-    const int64_t fdw = (int64_t)fs * H * W / 4;
+    const int fdw = frame_dwords(fs, H * W);
     bool ok = (units % 2) == 0 && units < (1 << 22) && W % 4 == 0;
     for (int64_t u = 0; ok && u < units; u++) {
         const int64_t q = ((uint64_t)u * g.mag_ups) >> 32, r0 = u - q * g.ups;
@@ -341,43 +343,23 @@ static LeanGeom lean_geom(const snake_cfg *c)
     for (int64_t x = 0; ok && x < (int64_t)H * W / 4; x++)
         ok = (W / 4 == 1 ? x : (int64_t)(((uint64_t)x * g.mag_wpr) >> 32)) == x / (W / 4);
     g.exact = ok ? 1 : 0;
-    g.lean = ok && fdw > 8 * kWave && fdw <= 8 * 256 && g.lds_lean_bytes <= 48 * 1024 ? 1 : 0;
+    g.lean = ok && fdw > kTblDwordsMax && fdw <= kLeanDwordsMax && g.lds_lean_bytes <= 48 * 1024 ? 1 : 0;
     return g;
 }
 
-// Queue entries per shard: k_logic's blocks of E envs spread over kQShards
-// shards, room for every env of a shard's blocks.
-static int64_t queue_cap(int64_t N, int64_t E)
+// Validation and the buffer sizes. Also hands on the two facts of the config
+// that the sizes and the launch plan (build_kcfg) share, each derived once: the
+// lean geometry *g and the background choice *bg.
+static int layout_of(const snake_cfg *c, int64_t N, snake_layout *o, LeanGeom *g, bool *bg)
 {
-    const int64_t blocks = (N + E - 1) / E;
-    return (blocks + kQShards - 1) / kQShards * E;
-}
-
-// The fused step's area of resetq (snake_kernels.hip k_step), after the
-// kQSets queue sets: 64 logic-done counts (one line each), the groups' done and claim
-// flags (at most N / 4 groups), the encodes' hand-off records (uint4 per env).
-int64_t fused_base(int64_t N)
-{
-    const int64_t cap = std::max(queue_cap(N, 4), std::max(queue_cap(N, 8), queue_cap(N, 16)));
-    return round_up(kQSets * (kNumQ * kQShards * cap + kQCounters), 4);
-}
-int64_t fused_words(int64_t N)
-{
-    return kQShards * kQSpread + 2 * round_up((N + 3) / 4, 4) + 4 * N;
-}
-
-int layout_of(const snake_cfg *c, int64_t N, snake_layout *o)
-{
-    int rc = check_cfg(c);
-    if (rc) return rc;
+    if (int rc = check_cfg(c)) return rc;
     if (N < 1 || N > (int64_t)1 << 26) {
         set_error("num_envs must be in [1, 2^26] (got %lld)", (long long)N);
         return SNAKE_E_ARG;
     }
     memset(o, 0, sizeof *o);
     const int64_t S = c->num_snakes, fs = c->frame_stack, HW = (int64_t)c->height * c->width;
-    const int oh = c->vision_range ? 2 * c->vision_range + 1 : c->height;
-    const int ow = c->vision_range ? 2 * c->vision_range + 1 : c->width;
+    const int oh = obs_window(c->vision_range, c->height), ow = obs_window(c->vision_range, c->width);
     o->grid_stride = (int32_t)round_up(HW, 16);
     // >= 16: the step reads the rings as aligned 8-byte chunks and writes 4-byte words
     o->ring_cap = std::max(16, pow2_at_least((c->height - 2) * (c->width - 2)));
@@ -393,21 +375,19 @@ int layout_of(const snake_cfg *c, int64_t N, snake_layout *o)
     o->cand = o->n_cand * c->snake_length * 2;
     // What the reset workers record of a permutation (snake_kernels.hip
     // perm_trace): the u16 draw record in LDS up to kJarrLdsMax bytes, else one
-    // global u32 link table per reset worker.
+    // global u32 link table per reset worker (workers_global_links).
     const int64_t link = (round_up(o->n_cand, 4) + kWave) * 4;
-    // (also the four-wave lean-encode boards' auto-resets: k_post_lean's workers
-    // keep no draw record in LDS)
-    const bool lean_workers = c->autoreset == 1 && lean_geom(c).lean;
-    o->jscratch = (round_up(2 * (o->n_cand + kWave), 16) <= kJarrLdsMax && !lean_workers)
-                      ? 0 : std::min<int64_t>(N, kResetSlots) * link;
+    *g = lean_geom(c);
+    o->jscratch = workers_global_links(draw_record_fits(o->n_cand), g->lean, c->autoreset)
+                      ? std::min<int64_t>(N, kResetSlots) * link : 0;
     // (background spawn-ahead: one record per queue set and env, see k_spawn)
-    o->spawn = (bg_of(c, o->n_cand, N) ? kQSets : 1) * N * kSpawnStride * 4;
-    {   // auto-reset and spawn-ahead queues: kQShards shards each (k_logic block %
-        // kQShards) with room for every env of its blocks, + the step's counters
-        // (kQCount, each in its own line); sized for any k_logic lane grouping
-        // + the fused step's flags, counts and hand-off records
-        o->resetq = (fused_base(N) + fused_words(N)) * 4;
-    }
+    *bg = bg_of(c, o->n_cand, N);
+    o->spawn = (*bg ? kQSets : 1) * N * kSpawnStride * 4;
+    // auto-reset and spawn-ahead queues: kQShards shards each (k_logic block %
+    // kQShards) with room for every env of its blocks, + the step's counters
+    // (kQCount, each in its own line); sized for any k_logic lane grouping
+    // + the fused step's flags, counts and hand-off records
+    o->resetq = fused_area(N).end * 4;
     o->obs = N * S * oh * ow * 8 * fs;
     o->rew = N * S * 8;
     o->done = N * S;
@@ -437,17 +417,13 @@ int layout_of(const snake_cfg *c, int64_t N, snake_layout *o)
     return SNAKE_OK;
 }
 
-int build_kcfg(const snake_cfg *c, int64_t N, int64_t n_cand, KCfg *k)
+// ---- The stages of build_kcfg (below, in its order). Each fills one group of
+// KCfg's fields from its parameters and from the fields of earlier stages that
+// its comment names.
+
+// Stage 1, the config and board: what the cfg and the layout state as they are.
+static void plan_board(const snake_cfg *c, int64_t N, const snake_layout &lay, KCfg *k)
 {
-    snake_layout lay;
-    int rc = layout_of(c, N, &lay);
-    if (rc) return rc;
-    if (n_cand != lay.n_cand) {
-        set_error("spawn-pose table has %lld rows, expected %lld", (long long)n_cand,
-                  (long long)lay.n_cand);
-        return SNAKE_E_ARG;
-    }
-    memset(k, 0, sizeof *k);
     k->N = (int)N;
     k->H = c->height; k->W = c->width; k->HW = c->height * c->width;
     k->S = c->num_snakes; k->L = c->snake_length; k->vr = c->vision_range;
@@ -464,37 +440,45 @@ int build_kcfg(const snake_cfg *c, int64_t N, int64_t n_cand, KCfg *k)
     k->adv_j = (int)(a % k->ow); a /= k->ow;
     k->adv_i = (int)(a % k->oh); a /= k->oh;
     k->adv_k = (int)a;
+    k->rf = c->rew_fruit; k->rk = c->rew_kill; k->rl = c->rew_lose; k->rw = c->rew_win;
+    k->rt = c->rew_time; k->max_steps = c->max_episode_steps;
+}
+
+// Stage 2, the LDS of an encode without reset-worker state (k_encode's, and the
+// head of every worker's carve): the frames, centres and fruit buffer, then the
+// staged encode's groups and their reciprocals. Reads the board fields.
+static void plan_staged_encode(KCfg *k)
+{
     int off = 0;
     k->lds_frames = off; off += (int)round_up((int64_t)k->fs * k->grid_stride, 16);
     k->lds_centers = off; off += (int)round_up(4 * k->fs * kMaxSnakes, 16);
     k->lds_fruit = off; off += (int)round_up(2 * kMaxFruits, 16);
-    {   // staged encode: whole snakes per group, every group start 16-byte aligned
-        const int64_t P = (int64_t)k->oh * k->ow * 8 * k->fs;       // obs bytes per snake
-        int g = 0;
-        if ((int64_t)k->S * P <= kStageMax) {
-            g = k->S;
-        } else {
-            g = (int)std::min<int64_t>(k->S, kStageMax / P);
-            if (P % 16 != 0) g &= ~1;
-        }
-        k->enc_group = g;
-        k->lds_stage = off;
-        k->lds_worker = off;   // (frames, centres, fruit buffer: a resets-only worker without the draw record)
-        if (g > 0) off += (int)round_up(g * P, 16);
-        const uint64_t fsoh = (uint64_t)k->fs * k->oh, oh = (uint64_t)k->oh;
-        k->mag_fsoh = (uint32_t)(((1ull << 32) + fsoh - 1) / fsoh);
-        k->mag_oh = (uint32_t)(((1ull << 32) + oh - 1) / oh);
-        k->mag_W = (uint32_t)(((1ull << 32) + k->W - 1) / k->W);
-        const uint64_t n16 = (uint64_t)k->grid_stride / 16;
-        k->mag_n16 = (uint32_t)(((1ull << 32) + n16 - 1) / n16);
+    // staged encode: whole snakes per group, every group start 16-byte aligned
+    const int64_t P = (int64_t)k->oh * k->ow * 8 * k->fs;       // obs bytes per snake
+    int g = 0;
+    if ((int64_t)k->S * P <= kStageMax) {
+        g = k->S;
+    } else {
+        g = (int)std::min<int64_t>(k->S, kStageMax / P);
+        if (P % 16 != 0) g &= ~1;
     }
-    k->link_stride = (int)round_up(k->n_cand, 4) + kWave;
-    // the LDS draw record: u16 per index < n_cand + one dummy slot per lane
-    int jbytes = (int)round_up(2 * ((int64_t)k->n_cand + kWave), 16);
-    k->link_in_lds = jbytes <= kJarrLdsMax;
+    k->enc_group = g;
+    k->lds_stage = off;
+    k->lds_worker = off;   // (frames, centres, fruit buffer: a resets-only worker without the draw record)
+    if (g > 0) off += (int)round_up(g * P, 16);
+    k->lds_obs_bytes = off;
+    k->mag_fsoh = mag((uint64_t)k->fs * k->oh); k->mag_oh = mag(k->oh);
+    k->mag_W = mag(k->W); k->mag_n16 = mag((uint64_t)k->grid_stride / 16);
+}
+
+// Stage 3, the spawn policy: the background choice bg (bg_of, made with the
+// layout), the workers' counts and priorities, the spawn-ahead threshold and
+// the attempts per job. Reads n_cand.
+static void plan_spawn(const snake_cfg *c, int64_t N, bool bg, KCfg *k)
+{
+    const int64_t n_cand = k->n_cand;
     // reset workers (<= kResetSlots, the global link tables are sized for that)
     k->reset_slots = (int)std::min<int64_t>(N, kResetSlots);
-    const bool bg = bg_of(c, n_cand, N);
     // small boards with the background kernel: the workers only paint resets
     // from records (≈65 per step at cfg2), so 512 of them (same box, ms per
     // step: cfg2 0.0399 -> 0.0394 and 0.0401 -> 0.0397; 256: 0.0397; 40x40
@@ -513,14 +497,35 @@ int build_kcfg(const snake_cfg *c, int64_t N, int64_t n_cand, KCfg *k)
     // spawn-ahead the step's resets are the critical path beside the encodes
     // instead: 0 (cfg5 0.160 -> 0.135 ms).
     k->encode_prio = bg ? 0 : 2;   // (2 on small background boards: cfg2 0.0399 -> 0.0403)
-    {
-        // k_logic's lanes per env (4, 8 or 16 >= S; 64 / that = envs per wave):
-        // the fewest lanes that hold S snakes; small batches at least 8 (more,
-        // shorter waves: cfg2's 4 096 envs k_logic 16.4 -> 15.3 us, step 0.0540
-        // -> 0.0527 ms; 16 lanes 18.0 us; at cfg3 8 lanes cost 6 us)
-        const int ms_min = k->S <= 4 ? 4 : (k->S <= 8 ? 8 : 16);
-        k->logic_ms = N <= 8192 ? std::max(ms_min, 8) : ms_min;   // (round 5, background cfg2: 4 lanes 0.0403 vs 0.0399)
-    }
+    k->spawn_thr = spawn_thr_of(c);
+    // small batches with the background kernel: the attempts leave the step and
+    // the CUs have room, so one live snake more (round 5, same box, ms per step,
+    // threshold 3 -> 4: cfg2 0.0409 -> 0.0403, cfg3 geometry at 8 192 envs
+    // 0.0434 -> 0.0425; 40x40 boards unchanged at 3: cfg5 0.0826 vs 0.0827)
+    if (bg_small && c->spawn_ahead == 0 && !c->coop && k->spawn_thr == 3) k->spawn_thr = 4;
+    k->bg = bg ? 1 : 0;
+    // k_spawn workers: 512 on small background boards (≈130 jobs per step at
+    // cfg2: 0.0397 -> 0.0391 ms, same box; 256: 0.0392), 2 048 on 40x40 (cfg5:
+    // 512 0.0827-0.0832, 1 024 0.0822, 2 048 0.0823)
+    k->spawn_slots = (int)std::min<int64_t>(N, bg_small ? 512 : kResetSlots);
+    // k_spawn: attempts per job. Two on small background boards since the four
+    // queue sets (round 6, same box, ms per step: cfg2 0.0397 -> 0.0380, cfg3s8
+    // 0.0414 -> 0.0401; four tries slower, profiles/r06_ab_qsets.txt); one on
+    // 40x40 (4 measured 0.30 ms at cfg5: the kernel then gates k_logic)
+    k->bg_tries = bg_small ? SNAKE_BG_TRIES_SMALL : 1;
+    k->spawn_tries = 1;   // attempts per in-step spawn-ahead job (2 measured cfg3 0.0875 -> 0.103 ms: a retry doubles the chain)
+}
+
+// Stage 4, k_logic's shape: lanes per env, LDS per wave, waves per workgroup
+// and the queue capacity. Reads the board fields.
+static int plan_logic(int64_t N, KCfg *k)
+{
+    // k_logic's lanes per env (4, 8 or 16 >= S; 64 / that = envs per wave):
+    // the fewest lanes that hold S snakes; small batches at least 8 (more,
+    // shorter waves: cfg2's 4 096 envs k_logic 16.4 -> 15.3 us, step 0.0540
+    // -> 0.0527 ms; 16 lanes 18.0 us; at cfg3 8 lanes cost 6 us)
+    const int ms_min = lanes_per_env(k->S);
+    k->logic_ms = N <= 8192 ? std::max(ms_min, 8) : ms_min;   // (round 5, background cfg2: 4 lanes 0.0403 vs 0.0399)
     // k_logic's LDS carve (snake_kernels.hip k_logic) per wave: E frames, the
     // fruit buffer, the respawn raws and cells
     auto logic_lds = [&](int G) {
@@ -540,60 +545,39 @@ int build_kcfg(const snake_cfg *c, int64_t N, int64_t n_cand, KCfg *k)
     k->logic_wpb = 4 * (int64_t)k->lds_logic <= kLdsLimit ? 4 : 1;
     k->q_envs_per_block = kWave / k->logic_ms;
     k->q_cap = (int)queue_cap(N, k->q_envs_per_block);
-    k->spawn_thr = spawn_thr_of(c);
-    // small batches with the background kernel: the attempts leave the step and
-    // the CUs have room, so one live snake more (round 5, same box, ms per step,
-    // threshold 3 -> 4: cfg2 0.0409 -> 0.0403, cfg3 geometry at 8 192 envs
-    // 0.0434 -> 0.0425; 40x40 boards unchanged at 3: cfg5 0.0826 vs 0.0827)
-    if (bg_small && c->spawn_ahead == 0 && !c->coop && k->spawn_thr == 3) k->spawn_thr = 4;
-    k->bg = bg ? 1 : 0;
-    // k_spawn workers: 512 on small background boards (≈130 jobs per step at
-    // cfg2: 0.0397 -> 0.0391 ms, same box; 256: 0.0392), 2 048 on 40x40 (cfg5:
-    // 512 0.0827-0.0832, 1 024 0.0822, 2 048 0.0823)
-    k->spawn_slots = (int)std::min<int64_t>(N, bg_small ? 512 : kResetSlots);
-#ifndef SNAKE_BG_TRIES_SMALL
-#define SNAKE_BG_TRIES_SMALL 2
-#endif
-    // k_spawn: attempts per job. Two on small background boards since the four
-    // queue sets (round 6, same box, ms per step: cfg2 0.0397 -> 0.0380, cfg3s8
-    // 0.0414 -> 0.0401; four tries slower, profiles/r06_ab_qsets.txt); one on
-    // 40x40 (4 measured 0.30 ms at cfg5: the kernel then gates k_logic)
-    k->bg_tries = bg_small ? SNAKE_BG_TRIES_SMALL : 1;
-    k->spawn_tries = 1;   // attempts per in-step spawn-ahead job (2 measured cfg3 0.0875 -> 0.103 ms: a retry doubles the chain)
-    k->lds_obs_bytes = off;
-    {
-        const LeanGeom g = lean_geom(c);
-        k->lean = g.lean; k->lp = g.lp; k->pw = g.pw; k->pframe = g.pframe;
-        k->lds_lean_bytes = g.lds_lean_bytes; k->ups = g.ups; k->rowl = g.rowl;
-        k->mag_ups = g.mag_ups; k->mag_rowl = g.mag_rowl; k->mag_fs = g.mag_fs; k->mag_wpr = g.mag_wpr;
-        // the table encode (snake_kernels.hip encode_tbl_block) where k_post runs
-        // the encodes: rings of at most 512 dwords, the lean geometry exact
-        const int64_t fdw = (int64_t)k->fs * k->HW / 4;
-        int t = 0;
-        k->tbl_base = (int)round_up((int64_t)k->fs * k->pframe, 16); t = k->tbl_base + 8 * k->fs * kMaxSnakes;
-        // patterns: the largest grid byte is 10 * (S - 1) + 5, so 10 * S entries per snake
-        k->tbl_patv = 10 * k->S;
-        k->tbl_pat = t; t += 8 * k->S * k->tbl_patv;
-        // descriptors: carved only where they are read from LDS -- the four-wave
-        // form, and one wave with more than four 16-byte chunks per lane (else
-        // each lane computes its four pairs into registers)
-        k->tbl_desc = t;
-        if (g.lean || k->units / 2 > 4 * kWave) t += (int)round_up(4 * (int64_t)k->units, 16);
-        k->lds_tbl_bytes = (int)round_up(t, 16);
-        auto mag = [](uint64_t d) { return (uint32_t)(((1ull << 32) + d - 1) / d); };
-        k->mag_nw = mag((uint64_t)std::max(1, k->HW / 4));
-        k->mag_npv = mag(3 + 3 * (uint64_t)k->S);
-        k->mag_S = mag((uint64_t)k->S);
-        // (which boards take the table encode is still decided on the size of
-        // the full carve -- 160 pattern entries per snake and the descriptors --
-        // that the measurements behind these limits had)
-        const int64_t t_full = k->tbl_pat + 8 * k->S * 160 + round_up(4 * (int64_t)k->units, 16);
-        k->tbl = g.exact && !g.lean && fdw <= 8 * kWave && t_full <= 40 * 1024 ? 1 : 0;
-        // also in k_post_lean's four-wave workgroups (tables shared by the
-        // workgroup, two envs each): cfg5 0.1023-0.1031 -> 0.1013-0.1015 ms; four
-        // or eight envs per workgroup 0.107 / 0.111
-        if (g.lean && t_full <= 48 * 1024) k->tbl = 1;
-    }
+    return SNAKE_OK;
+}
+
+// Stage 5, the encode path of the step's shared phase: the lean geometry g
+// copied in, the table encode's carve and reciprocals, which boards take it
+// (tbl), and the envs per encode wave. Reads the board fields.
+static void plan_encode(int64_t N, const LeanGeom &g, KCfg *k)
+{
+    k->lean = g.lean; k->lp = g.lp; k->pw = g.pw; k->pframe = g.pframe;
+    k->lds_lean_bytes = g.lds_lean_bytes; k->ups = g.ups; k->rowl = g.rowl;
+    k->mag_ups = g.mag_ups; k->mag_rowl = g.mag_rowl; k->mag_fs = g.mag_fs; k->mag_wpr = g.mag_wpr;
+    // the table encode (snake_kernels.hip encode_tbl_block) where k_post runs
+    // the encodes: rings of at most 512 dwords, the lean geometry exact
+    int t = 0;
+    k->tbl_base = (int)round_up((int64_t)k->fs * k->pframe, 16); t = k->tbl_base + 8 * k->fs * kMaxSnakes;
+    // patterns: the largest grid byte is 10 * (S - 1) + 5, so 10 * S entries per snake
+    k->tbl_patv = 10 * k->S;
+    k->tbl_pat = t; t += 8 * k->S * k->tbl_patv;
+    // descriptors: carved only where they are read from LDS (tbl_desc_in_lds)
+    k->tbl_desc = t;
+    if (tbl_desc_in_lds(*k)) t += (int)round_up(4 * (int64_t)k->units, 16);
+    k->lds_tbl_bytes = (int)round_up(t, 16);
+    k->mag_nw = mag((uint64_t)std::max(1, k->HW / 4));
+    k->mag_npv = mag(3 + 3 * (uint64_t)k->S); k->mag_S = mag((uint64_t)k->S);
+    // (which boards take the table encode is still decided on the size of
+    // the full carve -- 160 pattern entries per snake and the descriptors --
+    // that the measurements behind these limits had)
+    const int64_t t_full = k->tbl_pat + 8 * k->S * 160 + round_up(4 * (int64_t)k->units, 16);
+    k->tbl = g.exact && !g.lean && frame_dwords(k->fs, k->HW) <= kTblDwordsMax && t_full <= 40 * 1024 ? 1 : 0;
+    // also in k_post_lean's four-wave workgroups (tables shared by the
+    // workgroup, two envs each): cfg5 0.1023-0.1031 -> 0.1013-0.1015 ms; four
+    // or eight envs per workgroup 0.107 / 0.111
+    if (g.lean && t_full <= 48 * 1024) k->tbl = 1;
     // envs per encode wave (k_post's encodes: the next env's ring prefetched into
     // registers, at most 8 16-byte chunks per lane): two at 16 384 envs and more
     // (cfg3 0.1033 -> 0.0998 ms; 4, 8, 16, 32 measured 0.1016, 0.106, 0.114,
@@ -602,6 +586,16 @@ int build_kcfg(const snake_cfg *c, int64_t N, int64_t n_cand, KCfg *k)
     if (k->tbl) k->enc_per_wave = k->lean ? 2 : SNAKE_TBL_EPW;   // (the tables are built once per wave; 8 measured slower at cfg3)
     // (k_logic encoding the observations of its envs itself, from its LDS frames,
     // measured slower: cfg3 k_logic 24.8 -> 83.9 us against k_post 66.9 -> 57.6)
+}
+
+// Stage 6, the reset workers' LDS: the permutation record they keep (u16 draw
+// record, u32 link table, or none: global link tables) and lds_bytes. Reads
+// n_cand, lds_stage and lds_obs_bytes (stage 2), bg (3), tbl and lean (5).
+static int plan_worker_lds(int64_t N, KCfg *k)
+{
+    k->link_stride = (int)round_up(k->n_cand, 4) + kWave;
+    int jbytes = (int)draw_record_bytes(k->n_cand);
+    k->link_in_lds = draw_record_fits(k->n_cand);
     // the reset workers never use the encode staging buffer: the draw record
     // overlays it (the workers' LDS is what k_encode's waves share the CUs with)
     k->lds_link = k->lds_stage;
@@ -614,15 +608,23 @@ int build_kcfg(const snake_cfg *c, int64_t N, int64_t n_cand, KCfg *k)
     // enc_wpb waves (below) share that charge, so with them the u32 table also
     // wins at 65 536 envs (cfg3 0.0825 -> 0.0774 ms, profiles/r07_ab_encode_blocks.txt);
     // larger batches are not measured and keep the u16 record
-    if (k->link_in_lds && !bg && 4 * (int64_t)k->link_stride <= kJarrLdsMax &&
+    if (k->link_in_lds && !k->bg && 4 * (int64_t)k->link_stride <= kJarrLdsMax &&
         (N <= 32768 || (N <= SNAKE_LINK32_MAX_ENVS && k->tbl && !k->lean))) {
         k->link32 = 1;
         jbytes = 4 * k->link_stride;
     }
-    k->lds_bytes = k->link_in_lds ? std::max(off, k->lds_stage + jbytes) : off;
-#ifndef SNAKE_ENC_WPB
-#define SNAKE_ENC_WPB kEncWpbMax
-#endif
+    k->lds_bytes = k->link_in_lds ? std::max(k->lds_obs_bytes, k->lds_stage + jbytes) : k->lds_obs_bytes;
+    if (k->lds_bytes > 64 * 1024) {
+        set_error("grid ring of %d bytes per env does not fit the LDS budget", k->ring_bytes);
+        return SNAKE_E_CONFIG;
+    }
+    return SNAKE_OK;
+}
+
+// Stage 7, the table encode's waves per workgroup. Reads tbl, lean and
+// lds_tbl_bytes (stage 5) and lds_bytes (stage 6).
+static void plan_encode_blocks(KCfg *k)
+{
     // k_post's table-encode waves per workgroup: every workgroup of the launch,
     // the workers' too, is charged the larger of the workers' LDS and enc_wpb
     // table carves, so as many waves as keep that at the workers' own size or
@@ -632,30 +634,48 @@ int build_kcfg(const snake_cfg *c, int64_t N, int64_t n_cand, KCfg *k)
     if (k->tbl && !k->lean)
         for (int w = 2; w <= std::min((int)SNAKE_ENC_WPB, kEncWpbMax); w++)
             if (w * k->lds_tbl_bytes <= std::max(k->lds_bytes, 10 * 1024)) k->enc_wpb = w;
-    if (k->lds_bytes > 64 * 1024) {
-        set_error("grid ring of %d bytes per env does not fit the LDS budget", k->ring_bytes);
-        return SNAKE_E_CONFIG;
-    }
-    {   // the fused step (snake_kernels.hip k_step): all-done auto-reset in the step
-        // with the one-wave table encode (4 envs per wave), one frame and at most
-        // 4 snakes (the hand-off record's crop centres), in-step spawn-ahead
-        const int E = kWave / k->logic_ms;
-        k->nlg = (int)((N + E - 1) / E);
-        k->fused = c->autoreset == 1 && k->tbl && !k->lean && !k->bg && k->fs == 1 && k->S <= 4 &&
-                   k->enc_per_wave == 4 && E % 4 == 0 && (k->link32 || k->link_in_lds) ? 1 : 0;
-        const int64_t fb = fused_base(N), groups = round_up((N + 3) / 4, 4);
-        k->fu_ldone = fb;
-        k->fu_done = fb + kQShards * kQSpread;
-        k->fu_claim = k->fu_done + groups;
-        k->fu_hoff = k->fu_claim + groups;
-        k->epoch = 0;
-    }
-    k->rf = c->rew_fruit; k->rk = c->rew_kill; k->rl = c->rew_lose; k->rw = c->rew_win;
-    k->rt = c->rew_time; k->max_steps = c->max_episode_steps;
+}
+
+// Stage 8, the fused step (snake_kernels.hip k_step): where it is eligible, its
+// logic groups and its area of resetq. Reads the stages above.
+static void plan_fused(const snake_cfg *c, int64_t N, KCfg *k)
+{
+    // all-done auto-reset in the step with the one-wave table encode (4 envs
+    // per wave), one frame and at most 4 snakes (the hand-off record's crop
+    // centres), in-step spawn-ahead
+    const int E = kWave / k->logic_ms;
+    k->nlg = (int)((N + E - 1) / E);
+    k->fused = c->autoreset == 1 && k->tbl && !k->lean && !k->bg && k->fs == 1 && k->S <= 4 &&
+               k->enc_per_wave == 4 && E % 4 == 0 && link_record(*k) != 0 ? 1 : 0;
+    const FusedArea fa = fused_area(N);
+    k->fu_ldone = fa.ldone; k->fu_done = fa.done; k->fu_claim = fa.claim; k->fu_hoff = fa.hoff;
+}
+
+// The launch plan of a config layout_of has accepted (lay, g, bg: its results); checks the launch side's limits.
+static int build_kcfg(const snake_cfg *c, int64_t N, const snake_layout &lay, const LeanGeom &g, bool bg, KCfg *k)
+{
+    memset(k, 0, sizeof *k);
+    plan_board(c, N, lay, k);
+    plan_staged_encode(k);
+    plan_spawn(c, N, bg, k);
+    if (int rc = plan_logic(N, k)) return rc;
+    plan_encode(N, g, k);
+    if (int rc = plan_worker_lds(N, k)) return rc;
+    plan_encode_blocks(k);
+    plan_fused(c, N, k);
     return SNAKE_OK;
 }
 
-static int check_state(const KCfg &k, const snake_state *st, bool need_all)
+// The whole plan of (cfg, num_envs) in one pass: validation, the buffer sizes
+// (*lay, written as far as layout_of got) and the kernels' configuration.
+static int plan_of(const snake_cfg *c, int64_t N, snake_layout *lay, KCfg *k)
+{
+    LeanGeom g; bool bg;
+    if (int rc = layout_of(c, N, lay, &g, &bg)) return rc;
+    return build_kcfg(c, N, *lay, g, bg, k);
+}
+
+static int check_state(const KCfg &k, const snake_state *st)
 {
     if (!st || !st->grid || !st->snake || !st->body || !st->env || !st->ctr || !st->stats ||
         !st->mt || !st->cand) {
@@ -666,11 +686,10 @@ static int check_state(const KCfg &k, const snake_state *st, bool need_all)
         set_error("snake_state.resetq / spawn is NULL");
         return SNAKE_E_ARG;
     }
-    if ((!k.link_in_lds || (k.lean && k.autoreset == 1)) && !st->jscratch) {
+    if (workers_global_links(k) && !st->jscratch) {
         set_error("snake_state.jscratch is required for this config (n_cand=%d)", k.n_cand);
         return SNAKE_E_ARG;
     }
-    (void)need_all;
     return SNAKE_OK;
 }
 
@@ -684,17 +703,10 @@ static int check_out(const snake_out *o, bool step)
     return SNAKE_OK;
 }
 
-static int64_t n_cand_of(const snake_cfg *c)
-{
-    snake_layout lay;
-    if (layout_of(c, 1, &lay)) return -1;
-    return lay.n_cand;
-}
-
-// build_kcfg of the step/reset/seed calls, memoised per thread: the plan is a
+// plan_of for the step/reset/seed calls, memoised per thread: the plan is a
 // pure function of (cfg, num_envs) (the environment knobs are read once), and
 // re-planning on every snake_step cost host time on the step's critical path
-// at small N (layout_of twice, two mutex-guarded table lookups).
+// at small N (the layout, two mutex-guarded table lookups).
 static int plan_cached(const snake_cfg *c, int64_t N, KCfg *k)
 {
     struct Entry {
@@ -711,8 +723,8 @@ static int plan_cached(const snake_cfg *c, int64_t N, KCfg *k)
             return SNAKE_OK;
         }
     }
-    int rc = build_kcfg(c, N, n_cand_of(c), k);
-    if (rc) return rc;
+    snake_layout lay;
+    if (int rc = plan_of(c, N, &lay, k)) return rc;
     Entry &e = memo[next];
     e.cfg = *c;
     e.n = N;
@@ -736,22 +748,17 @@ int snake_plan(const snake_cfg *cfg, int64_t num_envs, snake_layout *out)
 {
     if (!out) { set_error("out is NULL"); return SNAKE_E_ARG; }
     g_err[0] = 0;
-    int rc = layout_of(cfg, num_envs, out);
-    if (rc) return rc;
     // (and every launch-side limit: a config the step cannot launch fails here)
     KCfg k;
-    return build_kcfg(cfg, num_envs, out->n_cand, &k);
+    return plan_of(cfg, num_envs, out, &k);
 }
 
 int snake_plan_paths(const snake_cfg *cfg, int64_t num_envs, snake_paths *out)
 {
     if (!out) { set_error("out is NULL"); return SNAKE_E_ARG; }
     g_err[0] = 0;
-    snake_layout lay;
-    int rc = layout_of(cfg, num_envs, &lay);
-    if (rc) return rc;
-    KCfg k;
-    if ((rc = build_kcfg(cfg, num_envs, lay.n_cand, &k))) return rc;
+    snake_layout lay; KCfg k;
+    if (int rc = plan_of(cfg, num_envs, &lay, &k)) return rc;
     memset(out, 0, sizeof *out);
     // the all-done auto-reset step encodes in k_post / k_post_lean (TBL, NPF < 0,
     // else encode_obs); the other modes in k_encode, which is encode_obs only
@@ -762,12 +769,10 @@ int snake_plan_paths(const snake_cfg *cfg, int64_t num_envs, snake_paths *out)
     out->units = k.units;
     out->enc_per_wave = post ? k.enc_per_wave : 1;
     out->enc_wpb = post ? k.enc_wpb : 1;
-    // (build_kcfg's carve of tbl_desc)
-    out->desc_in_lds = post && k.tbl && (k.lean || k.units / 2 > 4 * kWave) ? 1 : 0;
+    out->desc_in_lds = post && k.tbl && tbl_desc_in_lds(k) ? 1 : 0;
     out->fused = k.fused;
     out->background = k.bg;
-    // k_post_lean's auto-reset workers keep no record in LDS whatever fits (snake_launch.inc launch_post)
-    out->link = k.lean && k.autoreset == 1 ? 0 : (k.link32 ? 2 : (k.link_in_lds ? 1 : 0));
+    out->link = workers_global_links(k) ? 0 : link_record(k);
     out->logic_lanes = k.logic_ms;
     out->logic_wpb = k.logic_wpb;
     return SNAKE_OK;
@@ -795,7 +800,7 @@ int snake_seed(const snake_cfg *cfg, const snake_state *st, int64_t num_envs, ui
     KCfg k;
     int rc = plan_cached(cfg, num_envs, &k);
     if (rc) return rc;
-    if ((rc = check_state(k, st, false))) return rc;
+    if ((rc = check_state(k, st))) return rc;
     if (env_offset < 0) { set_error("env_offset < 0"); return SNAKE_E_ARG; }
     return launch_seed(k, *st, base_seed, env_offset, stream);
 }
@@ -806,7 +811,7 @@ int snake_reset(const snake_cfg *cfg, const snake_state *st, int64_t num_envs,
     KCfg k;
     int rc = plan_cached(cfg, num_envs, &k);
     if (rc) return rc;
-    if ((rc = check_state(k, st, true))) return rc;
+    if ((rc = check_state(k, st))) return rc;
     if ((rc = check_out(out, false))) return rc;
     return launch_reset(k, *st, env_mask, *out, stream);
 }
@@ -826,7 +831,7 @@ int snake_step(const snake_cfg *cfg, const snake_state *st, int64_t num_envs, co
     KCfg k;
     int rc = plan_cached(cfg, num_envs, &k);
     if (rc) return rc;
-    if ((rc = check_state(k, st, true))) return rc;
+    if ((rc = check_state(k, st))) return rc;
     if ((rc = check_out(out, true))) return rc;
     if (!actions) { set_error("actions is NULL"); return SNAKE_E_ARG; }
     return launch_step(k, *st, actions, *out, stream);

@@ -135,11 +135,56 @@ struct KCfg {
     double rf, rk, rl, rw, rt, max_steps;
 };
 
-int build_kcfg(const snake_cfg *c, int64_t num_envs, int64_t n_cand, KCfg *k);
-int layout_of(const snake_cfg *c, int64_t num_envs, snake_layout *out);
-// word offset in resetq of the fused step's area (after the kQSets queue sets), and its words
-int64_t fused_base(int64_t num_envs);
-int64_t fused_words(int64_t num_envs);
+// ---- The launch rules, each stated once (DESIGN.md "The env-step planner"):
+// the planner (snake_capi.cpp) and the launchers (snake_launch.inc) both read
+// them here. Host arithmetic only.
+constexpr int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
+// x / d == umulhi(x, mag(d)) for the ranges the planner checks or the kernels use
+constexpr uint32_t mag(uint64_t d) { return (uint32_t)(((1ull << 32) + d - 1) / d); }
+// the observation window's height (full = H) or width (full = W)
+constexpr int obs_window(int vr, int full) { return vr ? 2 * vr + 1 : full; }
+// k_logic's fewest lanes per env, one per snake; the MS of every other kernel
+constexpr int lanes_per_env(int S) { return S <= 4 ? 4 : (S <= 8 ? 8 : 16); }
+// the LDS draw record: u16 per index < n_cand + one dummy slot per lane
+constexpr int64_t draw_record_bytes(int64_t n_cand) { return round_up(2 * (n_cand + kWave), 16); }
+constexpr bool draw_record_fits(int64_t n_cand) { return draw_record_bytes(n_cand) <= kJarrLdsMax; }
+// dwords of one env's grid ring as the table and lean encodes copy it, and per
+// lane of a table-encode wave; the rings the two encodes take
+constexpr int frame_dwords(int fs, int HW) { return fs * HW / 4; }
+constexpr int kTblDwordsMax = 8 * kWave, kLeanDwordsMax = 8 * 256;
+constexpr int tbl_dwords_per_lane(const KCfg &k) { return (frame_dwords(k.fs, k.HW) + kWave - 1) / kWave; }
+constexpr int tbl_npw(const KCfg &k) { return tbl_dwords_per_lane(k) <= 2 ? 2 : 8; }   // the table encode's NPW: k_post's -NPF, k_step's
+// the table encode reads its unit descriptors from LDS: the four-wave form, and
+// one wave with more than four 16-byte chunks per lane (else each lane computes
+// its four pairs into registers)
+constexpr bool tbl_desc_in_lds(const KCfg &k) { return k.lean || k.units / 2 > 4 * kWave; }
+// the permutation record the plan carves for a reset: 0 global link tables,
+// 1 u16 draw record in LDS, 2 u32 link table in LDS (k_reset's and k_post's JL)
+constexpr int link_record(const KCfg &k) { return k.link32 ? 2 : (k.link_in_lds ? 1 : 0); }
+// the step's auto-reset workers use the global link tables (snake_state.jscratch):
+// no record fits LDS, or they are k_post_lean's, which keep none whatever fits
+constexpr bool workers_global_links(bool fits, bool lean, int autoreset) { return !fits || (lean && autoreset == 1); }
+constexpr bool workers_global_links(const KCfg &k) { return workers_global_links(k.link_in_lds, k.lean, k.autoreset); }
+
+// Queue entries per shard: k_logic's blocks of E envs spread over kQShards
+// shards, room for every env of a shard's blocks.
+constexpr int64_t queue_cap(int64_t N, int64_t E) { return ((N + E - 1) / E + kQShards - 1) / kQShards * E; }
+// The fused step's area of resetq (snake_kernels.hip k_step), after the kQSets
+// queue sets (sized for any k_logic lane grouping), as word offsets: 64
+// logic-done counts (one line each), the groups' done and claim flags (at most
+// N / 4 groups), the encodes' hand-off records (uint4 per env), and its end.
+struct FusedArea {
+    int64_t ldone, done, claim, hoff, end;
+};
+constexpr FusedArea fused_area(int64_t N)
+{
+    const int64_t c4 = queue_cap(N, 4), c8 = queue_cap(N, 8), c16 = queue_cap(N, 16);
+    const int64_t cap = c4 > c8 ? (c4 > c16 ? c4 : c16) : (c8 > c16 ? c8 : c16);
+    const int64_t base = round_up(kQSets * (kNumQ * kQShards * cap + kQCounters), 4);
+    const int64_t groups = round_up((N + 3) / 4, 4), done = base + kQShards * kQSpread;
+    return {base, done, done + groups, done + 2 * groups, done + 2 * groups + 4 * N};
+}
+
 void set_error(const char *fmt, ...);
 // after a kernel launch: SNAKE_OK, or SNAKE_E_LAUNCH and the error "<what> launch failed: <the runtime's message>"
 int launched(const char *what);

@@ -235,9 +235,6 @@ static inline void pick(int v, F &&f)
 }
 #define PICKED(x) decltype(x)::value
 
-static inline int ms_of(int S) { return S <= 4 ? 4 : (S <= 8 ? 8 : 16); }   // lanes per env, one per snake
-static inline int jl_of(const KCfg &k) { return k.link32 ? 2 : (k.link_in_lds ? 1 : 0); }   // autoreset_worker's JL
-
 int launch_reset(const KCfg &k, const snake_state &st, const uint8_t *mask, const snake_out &o, void *stream)
 {
     const dim3 grid(k.link_in_lds ? k.N : k.reset_slots), block(kWave);
@@ -247,8 +244,8 @@ int launch_reset(const KCfg &k, const snake_state &st, const uint8_t *mask, cons
     TimedLaunch tl("k_reset", (hipStream_t)stream);
     const KArgs a{k, st, o, mask};
     const hipStream_t s = (hipStream_t)stream;
-    pick<0, 1, 2>(jl_of(k), [&](auto jl) {
-        pick<4, 8, 16>(ms_of(k.S), [&](auto ms) {
+    pick<0, 1, 2>(link_record(k), [&](auto jl) {
+        pick<4, 8, 16>(lanes_per_env(k.S), [&](auto ms) {
             slaunch((k_reset<PICKED(ms), PICKED(jl)>), grid, block, k.lds_bytes, s, a);
         });
     });
@@ -272,8 +269,7 @@ static PostShape post_shape(const KCfg &k)
         return {0, dim3((k.reset_slots + 3) / 4 + (k.N + epw - 1) / epw), dim3(256),
                 std::max(4 * k.lds_worker, k.tbl ? k.lds_tbl_bytes : k.lds_lean_bytes)};
     const int n16 = k.ring_bytes >> 4;
-    const int npw = (k.fs * k.HW / 4 + kWave - 1) / kWave;   // frame dwords per lane (table encode)
-    const int npf = k.tbl ? (npw <= 2 ? -2 : -8) : (epw <= 1 ? 0 : (n16 <= kWave ? 1 : (n16 <= 2 * kWave ? 2 : 8)));
+    const int npf = k.tbl ? -tbl_npw(k) : (epw <= 1 ? 0 : (n16 <= kWave ? 1 : (n16 <= 2 * kWave ? 2 : 8)));
     const int enc_waves = npf == 0 ? k.N : (k.N + epw - 1) / epw;
     // the table encode: enc_wpb independent waves per workgroup, each with its own carve
     const int wpb = k.tbl ? k.enc_wpb : 1;
@@ -282,19 +278,19 @@ static PostShape post_shape(const KCfg &k)
 }
 
 // k_post_lean<MS(S), RO(bg), TBL> or k_post<MS(S), NPF, RO, JL>: resets only (ro: background
-// boards, which keep the LDS record, JL = 1) or the workers' whole job list with the link table jl
+// boards, whose link_record is 1) or the workers' whole job list with the link table jl
 static void launch_post(const KArgs &a, const PostShape &p, bool ro, int jl, hipStream_t s)
 {
     if (a.c.lean)
         return pick<0, 1>(a.c.tbl ? 1 : 0, [&](auto tbl) {
             pick<0, 1>(a.c.bg ? 1 : 0, [&](auto bg) {
-                pick<4, 8, 16>(ms_of(a.c.S), [&](auto ms) {
+                pick<4, 8, 16>(lanes_per_env(a.c.S), [&](auto ms) {
                     slaunch((k_post_lean<PICKED(ms), PICKED(bg) != 0, PICKED(tbl) != 0>), p.grid, p.block, p.lds, s, a);
                 });
             });
         });
     auto go = [&](auto ro_c, auto jl_c) {
-        pick<4, 8, 16>(ms_of(a.c.S), [&](auto ms) {
+        pick<4, 8, 16>(lanes_per_env(a.c.S), [&](auto ms) {
             pick<0, 1, 2, -2, -8, 8>(p.npf, [&](auto npf) {
                 slaunch((k_post<PICKED(ms), PICKED(npf), PICKED(ro_c) != 0, PICKED(jl_c)>), p.grid, p.block, p.lds, s, a);
             });
@@ -323,19 +319,18 @@ static int launch_fused(KCfg &k, const snake_state &st, const int8_t *actions, c
         if (it == g_fu.end()) { it = g_fu.emplace(st.env, 0u).first; fresh = true; }
         ep = it->second;
     }
-    if (fresh && hipMemsetAsync(st.resetq + k.fu_ldone, 0, sizeof(int) * fused_words(k.N), sm) != hipSuccess) {
+    if (fresh && hipMemsetAsync(st.resetq + k.fu_ldone, 0, sizeof(int) * (fused_area(k.N).end - k.fu_ldone), sm) != hipSuccess) {
         set_error("zeroing the fused step's flags failed");
         return SNAKE_E_LAUNCH;
     }
     k.epoch = ep + 1;
-    const int npw = (k.fs * k.HW / 4 + kWave - 1) / kWave;
     const dim3 gf(k.nlg + k.reset_slots + (k.N + 3) / 4), bf(kWave);
     const int lds_f = std::max(k.lds_logic, std::max(k.lds_bytes, k.lds_tbl_bytes));
     const KArgs fa{k, st, o, actions};
     TimedLaunch tf("k_step", sm);
     pick<4, 8>(k.logic_ms, [&](auto ms) {
-        pick<2, 8>(npw <= 2 ? 2 : 8, [&](auto npw_c) {
-            pick<2, 1>(k.link32 ? 2 : 1, [&](auto jl) {
+        pick<2, 8>(tbl_npw(k), [&](auto npw_c) {
+            pick<2, 1>(link_record(k), [&](auto jl) {
                 slaunch((k_step<PICKED(ms), PICKED(npw_c), PICKED(jl)>), gf, bf, lds_f, sm, fa);
             });
         });
@@ -410,10 +405,10 @@ static int launch_spawn(const KCfg &k, const snake_state &st, const snake_out &o
     }
     KCfg ks = k;
     ks.lds_link = 0;   // (only the draw record)
-    const int lds_sp = (int)(((int64_t)2 * (k.n_cand + kWave) + 15) / 16 * 16);
+    const int lds_sp = (int)draw_record_bytes(k.n_cand);
     TimedLaunch t4("k_spawn", bx);
     const KArgs sa{ks, st, o, nullptr};
-    pick<4, 8, 16>(ms_of(k.S), [&](auto ms) {
+    pick<4, 8, 16>(lanes_per_env(k.S), [&](auto ms) {
         slaunch(k_spawn<PICKED(ms)>, dim3(k.spawn_slots), dim3(kWave), lds_sp, bx, sa);
     });
     t4.close();
@@ -467,7 +462,7 @@ int launch_step(const KCfg &k0, const snake_state &st, const int8_t *actions, co
         const KArgs a{k, st, o, nullptr};
         TimedLaunch t2("k_autoreset", sm);
         pick<0, 1>(k.link_in_lds ? 1 : 0, [&](auto jl) {
-            pick<4, 8, 16>(ms_of(k.S), [&](auto ms) {
+            pick<4, 8, 16>(lanes_per_env(k.S), [&](auto ms) {
                 slaunch((k_autoreset<PICKED(ms), true, PICKED(jl)>), dim3(k.reset_slots), dim3(kWave), k.lds_bytes, sm, a);
             });
         });
@@ -480,7 +475,7 @@ int launch_step(const KCfg &k0, const snake_state &st, const int8_t *actions, co
     const KArgs a{k, st, o, nullptr};
     const PostShape shape = post_shape(k);
     TimedLaunch t2("k_post", sm);
-    launch_post(a, shape, k.bg != 0, jl_of(k), sm);
+    launch_post(a, shape, k.bg != 0, link_record(k), sm);
     t2.close();
     if ((rc = check_launch("k_post"))) return step_fail(k, st, bgc, bgc != nullptr, sm, rc);
 #ifdef SNAKE_DIAG_ENC2

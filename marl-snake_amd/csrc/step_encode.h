@@ -483,7 +483,7 @@ __device__ __forceinline__ void encode_tbl_body(const KCfg &c, const snake_state
     const int chunks = c.units >> 1;
     // a lane's chunks all in one pass (cfg3: 242 chunks): their descriptors
     // computed straight into registers for every env of the wave -- no LDS
-    // table (build_kcfg does not carve it), one LDS level less per lookup chain
+    // table (not carved: tbl_desc_in_lds), one LDS level less per lookup chain
     const bool one = T == kWave && chunks <= 4 * T;
     uint2 dr[4];
     if constexpr (T == kWave) if (one) {

@@ -66,8 +66,8 @@ def ring_cap(kw):
 
 
 def logic_lanes(S, N):
-    """Lanes per env of k_logic (build_kcfg): 4 / 8 / 16 for S <= 4 / 8 / 16, at
-    least 8 up to 8192 envs."""
+    """Lanes per env of k_logic (snake_capi.cpp plan_logic): 4 / 8 / 16 for
+    S <= 4 / 8 / 16 (lanes_per_env), at least 8 up to 8192 envs."""
     lanes = 4 if S <= 4 else (8 if S <= 8 else 16)
     return max(lanes, 8) if N <= 8192 else lanes
 

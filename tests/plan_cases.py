@@ -1,31 +1,40 @@
 """Which kernel path each named test shape is meant to take: the expected fields
 of snake_plan_paths (include/snake_env.h), written down by hand from the rules
-of build_kcfg (snake_capi.cpp) -- never read back from the library. The CPU test
+of the planner (snake_capi.cpp build_kcfg's stages, and the shared predicates of
+snake_internal.h) -- never read back from the library. The CPU test
 tests/test_plan_paths.py asserts the whole table; the GPU tests assert a case's
 row (check) before they step it, so a retuned threshold fails loudly instead of
-silently dropping a path's coverage.
+silently dropping a path's coverage. tests/test_plan_consistency.py holds the
+plan's fields to each other over a grid of shapes around every threshold.
 
 Rows: name -> (board kwargs, num_snakes, num_envs, expected fields). Only the
 fields that make the case what it is are listed.
 
 How the expected values follow from the shape (P = obs bytes per snake =
-oh * ow * 8 * frame_stack; fdw = frame_stack * H * W / 4 ring dwords):
-  lean    W % 4 == 0, an even unit count and 512 < fdw <= 2048
+oh * ow * 8 * frame_stack; fdw = frame_stack * H * W / 4 ring dwords,
+frame_dwords), and the function that states each rule:
+  lean    W % 4 == 0, an even unit count and 512 < fdw <= 2048 (lean_geom;
+          kTblDwordsMax, kLeanDwordsMax)
   table   W % 4 == 0, an even unit count, fdw <= 512 and the carve (image,
           window origins, 1280 * S pattern bytes, 4 * units descriptor bytes)
-          within 40 KB; on a lean board within 48 KB
+          within 40 KB; on a lean board within 48 KB (plan_encode)
   rows    otherwise, where at least one snake's P fits 8 KB: groups of
           min(S, 8192 // P) snakes, an even number where P % 16 != 0
+          (plan_staged_encode)
   direct  otherwise
   desc_in_lds   table encode with more than 256 unit pairs, or lean
+          (tbl_desc_in_lds)
   background    batches of at most 8192 envs and 64 MiB of observations, or more
           than 8192 spawn poses; never with spawn_background=-1 or a draw
-          record over 36 KB (more than 18 368 spawn poses: link 0)
+          record over 36 KB (more than 18 368 spawn poses: link 0) (bg_of,
+          draw_record_fits)
   link    2 (u32 table in LDS) without the background kernel up to 32 768
-          envs, else 1; 0 on lean boards (k_post_lean's workers) and over
-          18 368 poses
-  logic_lanes   4 / 8 / 16 for S <= 4 / 8 / 16, at least 8 up to 8192 envs
+          envs, else 1 (plan_worker_lds, link_record); 0 on lean boards
+          (k_post_lean's workers) and over 18 368 poses (workers_global_links)
+  logic_lanes   4 / 8 / 16 for S <= 4 / 8 / 16 (lanes_per_env), at least 8 up
+          to 8192 envs (plan_logic)
   logic_wpb     1 where four waves' frames (64 / lanes envs each) exceed 160 KB
+          (plan_logic)
 """
 DIRECT, ROWS, TABLE, LEAN, LEAN_TABLE = range(5)
 

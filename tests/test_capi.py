@@ -104,7 +104,7 @@ def test_plan_background_automatic(native, kw, N, bg):
 def test_plan_large_boards(native, H, W, L, N):
     """Boards whose k_logic frames do not fit four waves per workgroup (ADVICE r4:
     4 x 41 KB at 50x50 and 16 envs per wave) still plan: snake_plan runs the
-    launch-side checks too (build_kcfg), which pick one wave per workgroup or
+    launch-side checks too (build_kcfg's plan_logic), which pick one wave per workgroup or
     fewer envs per wave instead of a launch that fails."""
     c = cfg(native, height=H, width=W, snake_length=L, num_snakes=4, vision_range=3)
     lay = native.SnakeLayout()

@@ -1,6 +1,6 @@
 """snake_plan_paths (include/snake_env.h), the host-only description of the
 kernel variants snake_step takes: every shape the GPU tests name for a path
-(tests/plan_cases.py, expectations written down from build_kcfg's rules) still
+(tests/plan_cases.py, expectations written down from the planner's rules) still
 plans that path. No GPU needed."""
 import ctypes
 import os
