@@ -299,7 +299,8 @@ __global__ void __launch_bounds__(64) k_reset(const KArgs)
         if (mask && !mask[e]) continue;
         WaveMT mt;
         uint32_t cellw;
-        const int spst = load_reset_mt(J.c, J.st, e, mt, lane, true, cellw);
+        const int spst = J.c.bg ? load_reset_mt_bg(J.c, J.st, e, mt, lane, cellw)
+                                : load_reset_mt(J.c, J.st, e, mt, lane, true, cellw);
         do_reset<MS, JL>(J.c, J.st, J.o, e, mt, lds, blockIdx.x, spst, cellw, lane);
         // with spawn-ahead on, the next reset's poses are drawn now, off the step
         const KArgs &J2 = kargs(kp);

@@ -177,6 +177,28 @@ __device__ __forceinline__ int load_reset_mt(const KCfg &c, const snake_state &s
     return spw;
 }
 
+// load_reset_mt for an explicit reset (k_reset) under background spawn-ahead
+// (KCfg.bg): a k_spawn job publishes a record into its queue set's buffer and
+// names that buffer in the status word, so the record is read from there, not
+// from buffer 0. The launch is ordered after every background job
+// (wait_background), so plain loads see what the jobs published and no job is
+// drawing; a word still marked DRAWING counts as no record, as for a claim.
+__device__ __forceinline__ int load_reset_mt_bg(const KCfg &c, const snake_state &st, int64_t e, WaveMT &mt, int lane,
+                                                uint32_t &cellw)
+{
+    int spw = st.env[e * kEnvRec + ENV_SPAWN];
+    if ((spw & 3) == SPAWN_DRAWING) spw &= ~3;
+    cellw = 0;
+    if ((spw & 3) != SPAWN_NONE) {
+        const uint32_t *rec = spawn_rec(c, st, e, (spw >> kSpawnBufShift) & (kQSets - 1));
+        mt_load(mt, rec, (int)rec[kSpawnPos], lane);
+        cellw = rec[kSpawnCells + (lane >> 1)];
+    } else {
+        mt_load(mt, st.mt + e * kMtN, st.env[e * kEnvRec + ENV_MTPOS], lane);
+    }
+    return spw;
+}
+
 // Background spawn-ahead (KCfg.bg): an auto-reset takes env e's record with one
 // atomic that bumps the generation (a k_spawn job still working on the env then
 // fails its publish), and reads the record it found with sc1 loads.

@@ -63,18 +63,37 @@ class Net32:
     """One net in the kernel layout: `flat`, a zeroed float32 buffer on `device`
     (a cuda device or 'cpu'); `views`, the twelve tensors by the reference's
     names, views into it at offsets padded to 64 bytes; `struct`, the Dqn32Net
-    of their addresses."""
+    of their addresses. `flat=` gives the net a buffer of the caller's instead
+    (contiguous float32, Net32.size(P, C, A) elements, 16-byte aligned), used
+    as it is: nothing is zeroed."""
 
-    def __init__(self, P, C, A, device):
-        torch = get_torch()
-        self.P, self.C, self.A = P, C, A
+    @staticmethod
+    def spans(P, C, A):
+        """((offset, elements, shape) of the twelve tensors in FIELDS order, total elements)."""
         spans, off = [], 0
         for shape in kernel_shapes(P, C, A):
             size = shape[0] * (shape[1] if len(shape) == 2 else 1)
             spans.append((off, size, shape))
             off += (size + PAD - 1) // PAD * PAD
+        return spans, off
+
+    @classmethod
+    def size(cls, P, C, A):
+        return cls.spans(P, C, A)[1]
+
+    def __init__(self, P, C, A, device=None, flat=None):
+        torch = get_torch()
+        self.P, self.C, self.A = P, C, A
+        spans, off = self.spans(P, C, A)
         self.numel = off
-        self.flat = torch.zeros(off, dtype=torch.float32, device=device)
+        if flat is not None:
+            if flat.dtype != torch.float32 or flat.dim() != 1 or flat.numel() != off or not flat.is_contiguous():
+                raise ValueError('flat must be a contiguous float32 tensor of %d elements' % off)
+            if flat.data_ptr() % 16:
+                raise ValueError('flat must be 16-byte aligned')
+            self.flat = flat
+        else:
+            self.flat = torch.zeros(off, dtype=torch.float32, device=device)
         self.views = {name: self.flat[o:o + size].view(shape) for name, (o, size, shape) in zip(NAMES, spans)}
         base = self.flat.data_ptr()
         self.struct = Dqn32Net(*(base + 4 * o for o, _, _ in spans))

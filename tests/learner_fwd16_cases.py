@@ -32,6 +32,23 @@ ROUNDING_KEYS = ((5, 5, 8, 3, 0, 70), (5, 5, 24, 5, 0, 70), (20, 20, 8, 3, 0, 5)
 ROUNDING_SCALE = 61.0
 PREFIX_KEY, PREFIX_B = (5, 5, 8, 3, 1, 129), (1, 127, 129)
 
+# Two geometries for fc1's split K that tests/learner_cases.py's table lacks (the
+# table's fc1 chunks sit at the 1 024 floor, or end even):
+#   (17, 17, 8, 3, 0, 5)   K = 18 496, chunk 1 216 (above the floor), 16 chunks, the last of 256 steps
+#   (3, 11, 8, 3, 0, 37)   K = 2 112: three chunks, the last of 64 steps
+SPLIT_K_KEYS = ((17, 17, 8, 3, 0, 5), (3, 11, 8, 3, 0, 37))
+# largest probe activation and learner_cases.term_bound of the two, as computed once
+SPLIT_K_FACTS = {(17, 17, 8, 3, 0, 5): (117, 158020), (3, 11, 8, 3, 0, 37): (49, 86974)}
+# one more probe the guard-band tests run through the bf16 forward only
+# (tests/test_guard_dqn_gpu.py): five actions at 5x5x8
+FORWARD_ONLY_KEYS = ((5, 5, 8, 5, 0, 70),)
+
+
+def exact_runs():
+    """(key, B) of every run that must EQUAL the float64 reference: the learner
+    table's runs and the split-K geometries."""
+    return LC.gpu_backward_runs() + [(k, k[5]) for k in SPLIT_K_KEYS]
+
 
 # ---- the split-K rule of the dense layers (include/snake_env.h) ---------------------
 def split_k_chunk(K):

@@ -14,6 +14,8 @@ import numpy as np
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
+NAMES = ('obs', 'next_obs', 'actions', 'rewards', 'done', 'skip', 'step')     # push()'s arguments, in order
+
 
 class RefReplay:
     def __init__(self, capacity, early_death=None):
@@ -96,3 +98,20 @@ def replay_stream(d, buf_push):
         buf_push(d['obs'][t][None], d['next_obs'][t][None], d['action'][t][None].astype(np.int8),
                  d['reward'][t][None], d['done'][t][None].astype(np.uint8), d['mask'][t][None].astype(np.uint8),
                  d['step'][t:t + 1].astype(np.int32))
+
+
+def random_step(rs, N, S, h, w, C, p_skip=0.3):
+    """One env step's arrays: 0/1 observations, float64 rewards that float32
+    rounds, random dones, skip masks and episode steps around the threshold."""
+    return dict(obs=rs.randint(0, 2, size=(N, S, h, w, C)).astype(np.uint8),
+                next_obs=rs.randint(0, 2, size=(N, S, h, w, C)).astype(np.uint8),
+                actions=rs.randint(0, 3, size=(N, S)).astype(np.int8), rewards=rs.randn(N, S),
+                done=(rs.random_sample((N, S)) < 0.4).astype(np.uint8),
+                skip=(rs.random_sample((N, S)) < p_skip).astype(np.uint8),
+                step=rs.randint(0, 20, size=N).astype(np.int32))
+
+
+def push_both(torch, buf, ref, x):
+    """The same step into the device buffer and the restatement."""
+    buf.push(**{k: None if x.get(k) is None else torch.from_numpy(x[k]).cuda() for k in NAMES})
+    ref.push(*(x.get(k) for k in NAMES))

@@ -21,7 +21,7 @@ import learner_fwd16_cases as FC
 import learner_model as M
 from learner_gpu_util import key_ids, native, run_ids  # noqa: F401 (native is a fixture)
 
-ALL_RUNS = LC.gpu_backward_runs()
+ALL_RUNS = FC.exact_runs()
 RUN_IDS, KEY_IDS = run_ids(ALL_RUNS), key_ids(FC.ROUNDING_KEYS)
 
 
@@ -47,6 +47,31 @@ def test_probes_stage_only_bf16_values(key, B):
         assert bound < LC.SUM_LIMIT
         for name in LC.PARAMS:
             assert torch.equal(grads[name], case.grads[name]), name
+
+
+@pytest.mark.parametrize('key', FC.SPLIT_K_KEYS, ids=key_ids(FC.SPLIT_K_KEYS))
+def test_split_k_geometries_are_exact_probes(key):
+    """The two geometries added for fc1's split K: every activation of the probe
+    is a small integer and the largest sum of absolute gradient terms stays
+    below 2^24, so the forward and both backwards are exact in any order."""
+    case = LC.backward_case(key)
+    acts = P.ref64(case.state, case.obs)[2]
+    top = max(float(v.max()) for v in acts.values())
+    assert all(torch.equal(v, v.round()) and float(v.min()) >= 0 for v in acts.values())
+    bound = LC.term_bound(case.state, case.obs, case.dq)
+    print('%s: largest activation %g, term bound %g' % (key, top, bound))
+    assert (top, bound) == FC.SPLIT_K_FACTS[key] and bound < LC.SUM_LIMIT
+    for name in LC.PARAMS:
+        assert torch.equal(case.grads[name], case.grads[name].round()), name
+
+
+@pytest.mark.parametrize('key', FC.FORWARD_ONLY_KEYS, ids=key_ids(FC.FORWARD_ONLY_KEYS))
+def test_forward_only_probes_stage_only_bf16_values(key):
+    p = P.probe(*key)
+    model = M.forward_model(p.state, p.obs)
+    for name, v in model.staged.items():
+        assert torch.equal(v, v.round()) and float(v.abs().max()) < 256 and torch.equal(M.bf16(v), v), name
+    assert torch.equal(model.feat, p.feat) and torch.equal(model.q, p.q) and model.bound < LC.SUM_LIMIT
 
 
 def test_the_backward_chain_is_learner16_cases_chain():
@@ -160,6 +185,10 @@ def test_split_k_rule_and_the_cases_on_both_sides_of_it():
     assert FC.fc1_chunks((5, 5, 8, 3, 0, 70)) == (2, 576)
     assert FC.fc1_chunks((20, 20, 8, 3, 0, 5)) == (16, 1600)                                    # the most chunks, even
     assert FC.fc1_chunks(L16.REAL_GEOM) == (1, 768)
+    assert FC.split_k_chunk(64 * 17 * 17) == 1216 and FC.fc1_chunks((17, 17, 8, 3, 0, 5)) == (16, 256)    # above the floor, ragged
+    assert FC.split_k_chunk(64 * 3 * 11) == 1024 and FC.fc1_chunks((3, 11, 8, 3, 0, 37)) == (3, 64)
+    for key in FC.SPLIT_K_KEYS:
+        assert key in keys
     for key in FC.ROUNDING_KEYS + (FC.PREFIX_KEY,):
         assert key in keys
 

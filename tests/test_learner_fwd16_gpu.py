@@ -81,7 +81,7 @@ def localise(key, B, scale=1.0):
     return '; '.join(bad) or 'no single layer reproduces it'
 
 
-RUNS = LC.gpu_backward_runs()
+RUNS = FC.exact_runs()
 
 
 @pytest.mark.parametrize('key,B', RUNS, ids=run_ids(RUNS))

@@ -9,7 +9,7 @@ import replay_ref as R
 
 pytestmark = pytest.mark.gpu
 
-NAMES = ('obs', 'next_obs', 'actions', 'rewards', 'done', 'skip', 'step')
+NAMES = R.NAMES
 
 
 @pytest.fixture(scope='module')
@@ -25,21 +25,7 @@ def next_prime(n):
     return n
 
 
-def random_step(rs, N, S, h, w, C, p_skip=0.3):
-    """One env step's arrays: 0/1 observations, float64 rewards that float32
-    rounds, random dones, skip masks and episode steps around the threshold."""
-    return dict(obs=rs.randint(0, 2, size=(N, S, h, w, C)).astype(np.uint8),
-                next_obs=rs.randint(0, 2, size=(N, S, h, w, C)).astype(np.uint8),
-                actions=rs.randint(0, 3, size=(N, S)).astype(np.int8), rewards=rs.randn(N, S),
-                done=(rs.random_sample((N, S)) < 0.4).astype(np.uint8),
-                skip=(rs.random_sample((N, S)) < p_skip).astype(np.uint8),
-                step=rs.randint(0, 20, size=N).astype(np.int32))
-
-
-def push_both(torch, buf, ref, x):
-    """The same step into the device buffer and the restatement."""
-    buf.push(**{k: None if x.get(k) is None else torch.from_numpy(x[k]).cuda() for k in NAMES})
-    ref.push(*(x.get(k) for k in NAMES))
+random_step, push_both = R.random_step, R.push_both
 
 
 def assert_rows(got, want):
