@@ -739,6 +739,69 @@ int snake_replay_gather(const snake_replay_cfg *cfg, const snake_replay_rings *r
                         int64_t batch, int32_t format, void *state, void *next_state, int64_t *action,
                         float *reward, float *done, void *stream);
 
+/* ---- Python's `random` on the device: the one generator the reference
+ * trainer draws from -- random.random() < epsilon and random.randrange(A) per
+ * live snake (train_dqn.py:163-165), random.sample(buffer, B) per update
+ * (:96-97) -- so that a run seeded like random.seed(s) makes the reference's
+ * choices, draws its minibatch indices and leaves its generator state.
+ * (pyrandom_kernels.hip.)
+ *
+ * A stream is the 624 key words (uint32) and the position (int32, 0..624) of
+ * random.Random.getstate()[1]. The caller owns n streams in two device arrays,
+ * key [n][624] and pos [n]. With u32() the next tempered MT19937 word (a
+ * position of 624 twists the key first), CPython defines
+ *   getrandbits(k), 1 <= k <= 32   u32() >> (32 - k): the top bits;
+ *   _randbelow(n), 1 <= n < 2^31   k = n.bit_length(); getrandbits(k) until the
+ *                                  result is below n (a power of two n rejects
+ *                                  half of its words);
+ *   random()                       a = u32() >> 5, b = u32() >> 6, then
+ *                                  (a * 67108864 + b) / 2^53, exact in a double.
+ * Every rejection loop is bounded: after 256 words without a result -- a word
+ * rejects with probability below 9/16, no real stream gets there -- the call
+ * sets *err (device int32, zero it once; sticky: nothing ever clears it) and
+ * finishes with values inside the range. A position outside [0, 624] sets *err
+ * and is read as 624.
+ *
+ * Act. Env e uses stream e; its snakes are taken in slot order. A snake whose
+ * skip byte is nonzero gets action 0 and consumes nothing (:281-285). Every
+ * other snake draws u = random() -- both words, whatever epsilon is: the
+ * reference evaluates random.random() < epsilon whenever it trains -- and if
+ * u < epsilon (as doubles) its action is _randbelow(A), otherwise the first
+ * maximal index of its row of q (NaN Q-values are outside the contract). A step
+ * that crosses no key boundary reads the few words it consumes and writes the
+ * position only; a stream whose position reaches 624 with a word to draw has
+ * its key twisted in place.
+ *
+ * Sample. random.sample(range(n), B) from one stream, n = min(*count, capacity)
+ * read on the device (count: a replay buffer's counter):
+ *   setsize = 21, and for B > 5 also 4 ** ceil(log(3 B, 4)) (in integers: the
+ *   smallest power of four >= 3 B; 4117 at B = 512, 16405 at B = 4096);
+ *   n <= setsize: pool = [0, n); for i in 0..B-1: j = _randbelow(n - i),
+ *                 idx[i] = pool[j], pool[j] = pool[n - i - 1];
+ *   otherwise:    for i in 0..B-1: j = _randbelow(n) until j is not yet
+ *                 selected, idx[i] = j.
+ * The indices are logical (0 the oldest transition held), as snake_replay_gather
+ * takes them. Work and memory are O(B): nothing depends on the capacity.
+ * n < B is where Python raises: the call sets *err, draws nothing and writes
+ * indices inside [0, max(n, 1)). */
+
+/* Host only. SNAKE_E_CONFIG names the field: num_actions 1..127, batch 1..4096,
+ * capacity 1..2^31-1. Returns random.sample's setsize for `batch` (>= 21). */
+int snake_pyrandom_plan(int32_t num_actions, int64_t batch, int64_t capacity);
+
+/* q: float [N * S][A]; skip: uint8 [N][S] or NULL; key, pos: the first N
+ * streams; actions: int8 [N][S]. num_envs 0..2^26, num_snakes 1..16. One launch
+ * (k_pyrandom_act) on `stream`. */
+int snake_pyrandom_act(const float *q, const uint8_t *skip, double epsilon, uint32_t *key, int32_t *pos,
+                       int8_t *actions, int32_t *err, int64_t num_envs, int32_t num_snakes, int32_t num_actions,
+                       void *stream);
+
+/* key, pos: the stream arrays, of which stream `stream_index` is used; count:
+ * device int64; idx: int64 [batch]. One launch (k_pyrandom_sample, one wave) on
+ * `stream`. */
+int snake_pyrandom_sample(uint32_t *key, int32_t *pos, int64_t stream_index, const int64_t *count,
+                          int64_t capacity, int64_t batch, int64_t *idx, int32_t *err, void *stream);
+
 /* ---- Genome heads: a population of NEAT feed-forward networks, one genome
  * per env (train_ga.py:224-257 eval_genomes: every live snake's 128 features of
  * the frozen DQN go through the genome's neat.nn.FeedForwardNetwork, the action

@@ -9,6 +9,7 @@ from .envs import CoopSnakeEnv, GraphSnakeEnv, SnakeEnv  # noqa: F401
 from .vec_env import SnakeVecEnv  # noqa: F401
 from .dqn import DQNForward  # noqa: F401
 from .policy import SafeActions, evaluate  # noqa: F401
+from .pyrandom import PyRandom  # noqa: F401
 from .replay import Collector, ReplayBuffer  # noqa: F401
 from .learner import DQNLearner  # noqa: F401
 from .neat_head import GenomeHeads, evaluate_population  # noqa: F401

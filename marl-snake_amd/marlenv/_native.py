@@ -23,7 +23,8 @@ EXPORTS = ('snake_plan', 'snake_plan_paths', 'snake_build_candidates', 'snake_se
            'snake_graph_plan', 'snake_graph_weights', 'snake_graph_obs',
            'snake_dqn32_train_scratch', 'snake_dqn32_backward', 'snake_dqn_td_loss', 'snake_adam_step',
            'snake_dqn_pack32', 'snake_dqn_pack32_host', 'snake_dqn32_backward_bf16',
-           'snake_dqn32_forward_bf16_scratch', 'snake_dqn32_forward_bf16')
+           'snake_dqn32_forward_bf16_scratch', 'snake_dqn32_forward_bf16',
+           'snake_pyrandom_plan', 'snake_pyrandom_act', 'snake_pyrandom_sample')
 
 ADAM_SCRATCH_BYTES = 4112       # SNAKE_ADAM_SCRATCH_BYTES
 
@@ -206,6 +207,9 @@ def lib(path=None):
                                     I64, P, P]
     L.snake_replay_gather.argtypes = [ctypes.POINTER(ReplayCfg), ctypes.POINTER(ReplayRings), P, I64,
                                       ctypes.c_int32, P, P, P, P, P, P]
+    L.snake_pyrandom_plan.argtypes = [ctypes.c_int32, I64, I64]
+    L.snake_pyrandom_act.argtypes = [P, P, ctypes.c_double, P, P, P, P, I64, ctypes.c_int32, ctypes.c_int32, P]
+    L.snake_pyrandom_sample.argtypes = [P, P, I64, P, I64, I64, P, P, P]
     L.snake_genome_plan.argtypes = [ctypes.POINTER(GenomeCfg), I64, ctypes.POINTER(GenomeLayout)]
     L.snake_genome_check.argtypes = [ctypes.POINTER(GenomeCfg), ctypes.POINTER(GenomeProg)]
     L.snake_genome_tiles.argtypes = [ctypes.POINTER(GenomeCfg), P, P, I64, ctypes.c_int32, P, P, I64]

@@ -17,6 +17,7 @@ import ctypes
 
 from ._device import get_torch as _torch, stream_ptr
 from ._native import ReplayCfg, ReplayLayout, ReplayRings, check, lib
+from .pyrandom import PyRandom
 
 FORMATS = {'uint8': 0, 'float32': 1}
 
@@ -148,7 +149,7 @@ class ReplayBuffer:
         self._own_device()
         return self.count.clamp(max=self.capacity)
 
-    def sample(self, batch_size=None, idx=None, format='uint8', replace=False, generator=None):
+    def sample(self, batch_size=None, idx=None, format='uint8', replace=False, generator=None, rng=None, stream=0):
         """(state, action, reward, next_state, done): update_model's five
         tensors (train_dqn.py:236-240) -- action int64 (B,), reward and done
         float32 (B,), and the states as
@@ -164,22 +165,39 @@ class ReplayBuffer:
         the top batch_size of random keys over the slots held, replace=True by
         floor(u * size). The caller guarantees len(buf) >= batch_size (the
         reference's MIN_BUFFER_SIZE guard). generator: a torch.Generator of the
-        buffer's device."""
+        buffer's device.
+        rng: a PyRandom; the indices are then the reference's own
+        random.sample(self.buffer, batch_size) (:96-97) drawn from its stream
+        `stream` by snake_pyrandom_sample: one launch of O(batch_size) work,
+        whatever the capacity, at most 4096 indices from a capacity below 2^31.
+        It excludes idx and replace=True (ValueError)."""
         torch = _torch()
         if format not in FORMATS:
             raise ValueError("format must be 'uint8' or 'float32' (got %r)" % (format,))
+        if rng is not None:
+            if replace:
+                raise ValueError('rng draws random.sample, which does not repeat: replace=True cannot go with it')
+            if idx is not None:
+                raise ValueError('idx and rng exclude each other: idx is a pure gather')
+            if not isinstance(rng, PyRandom):
+                raise TypeError('rng must be a PyRandom (got %s)' % type(rng).__name__)
         if idx is None:
             if batch_size is None:
                 raise ValueError('sample needs batch_size or idx')
             B = int(batch_size)
             if B < 1 or (not replace and B > self.capacity):
                 raise ValueError('batch_size must be in [1, capacity] (got %d)' % B)
+            if rng is not None:
+                check(self._L.snake_pyrandom_plan(1, B, self.capacity), self._L)    # ValueError before any device work
             dev = self._own_device()
-            size = self.size()
-            if replace:
+            if rng is not None:
+                idx = rng.sample(self.count, self.capacity, B, stream=stream)
+            elif replace:
+                size = self.size()
                 u = torch.rand(B, device=dev, generator=generator, dtype=torch.float64)
                 idx = torch.minimum((u * size).to(torch.int64), size - 1)
             else:
+                size = self.size()
                 keys = torch.rand(self.capacity, device=dev, generator=generator)
                 held = torch.arange(self.capacity, device=dev) < size
                 idx = torch.topk(keys.masked_fill_(~held, -1.0), B).indices
@@ -249,27 +267,44 @@ class Collector:
         self.mask = torch.zeros((N, S), dtype=torch.bool, device=env.device)
         self.step_index = torch.zeros(N, dtype=torch.int32, device=env.device)
 
-    def run(self, qnet, steps, epsilon=0.0, generator=None):
+    def run(self, qnet, steps, epsilon=0.0, generator=None, rng=None):
         """`steps` env steps. qnet: any callable from uint8 (N*S, h, w, C)
         observations to float (N*S, 3) Q-values. Per snake u < epsilon gives a
         uniform action in {0, 1, 2}, otherwise the argmax; a snake that is
         already done gets action 0 (:281-285) and stores nothing. No host sync
-        inside the loop. generator: a torch.Generator of the env's device."""
+        inside the loop. generator: a torch.Generator of the env's device.
+        rng: a PyRandom with at least num_envs streams. Q-values then become
+        actions in one launch (snake_pyrandom_act) that reproduces the draws of
+        Agent.select_action (:163-165) from env e's stream e: per live snake in
+        slot order random.random() < epsilon -- drawn whatever epsilon is, as
+        the reference does while training -- and below it
+        random.randrange(A); a snake that is already done draws nothing. With
+        num_envs=1 and the stream seeded like random.seed(s) these are the
+        reference trainer's own choices for the same Q-values; the first
+        maximal Q-value wins a tie, as torch's argmax does."""
         torch = _torch()
         env, buf = self.env, self.buffer
         N, S = env.num_envs, env.num_snakes
         _, h, w, c = env.obs_shape
         dev = env.device
         eps = float(epsilon)
+        if rng is not None:
+            if not isinstance(rng, PyRandom):
+                raise TypeError('rng must be a PyRandom (got %s)' % type(rng).__name__)
+            if rng.n < N:
+                raise ValueError('%d envs need %d streams, this PyRandom has %d' % (N, N, rng.n))
         for _ in range(int(steps)):
             obs = self.obs
             q = qnet(obs.view(N * S, h, w, c))
-            greedy = q.reshape(N, S, -1).argmax(dim=2)
-            if eps > 0.0:
-                u = torch.rand((N, S), device=dev, generator=generator)
-                rnd = torch.randint(0, 3, (N, S), device=dev, generator=generator)
-                greedy = torch.where(u < eps, rnd, greedy)
-            actions = greedy.masked_fill(self.mask, 0).to(torch.int8)
+            if rng is not None:
+                actions = rng.act(q.reshape(N * S, -1), S, eps, skip=self.mask)
+            else:
+                greedy = q.reshape(N, S, -1).argmax(dim=2)
+                if eps > 0.0:
+                    u = torch.rand((N, S), device=dev, generator=generator)
+                    rnd = torch.randint(0, 3, (N, S), device=dev, generator=generator)
+                    greedy = torch.where(u < eps, rnd, greedy)
+                actions = greedy.masked_fill(self.mask, 0).to(torch.int8)
             next_obs, rewards, done, info = env.step(actions)
             ended = info['episode_done']
             buf.push(obs, next_obs, actions, rewards, done, skip=self.mask, step=self.step_index)
