@@ -19,9 +19,9 @@ import ctypes
 import numpy as np
 
 from ._device import get_torch as _torch, bind_device, ptr, skip_mask, stream_ptr
-from ._native import GenomeCfg, GenomeLayout, GenomeProg, GenomeTile, check, lib
+from ._native import DEFINES, GenomeCfg, GenomeLayout, GenomeProg, GenomeTile, check, lib
 
-RELU, SIGMOID, TANH = 0, 1, 2       # SNAKE_GENOME_RELU / _SIGMOID / _TANH
+RELU, SIGMOID, TANH = (DEFINES['SNAKE_GENOME_' + n] for n in ('RELU', 'SIGMOID', 'TANH'))
 _ACT = {'relu_activation': RELU, 'relu': RELU, 'sigmoid_activation': SIGMOID, 'sigmoid': SIGMOID,
         'tanh_activation': TANH, 'tanh': TANH}
 _AGG = ('sum_aggregation', 'sum')

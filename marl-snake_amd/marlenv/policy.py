@@ -13,9 +13,9 @@ DQN_Evaluator.evaluate.
 import ctypes
 
 from ._device import get_torch as _torch, bind_device, ptr, skip_mask, stream_ptr
-from ._native import PolicyCfg, check, lib
+from ._native import DEFINES, PolicyCfg, check, lib
 
-DIR_UNKNOWN = -128      # SNAKE_DIR_UNKNOWN: both bytes of a direction not known yet
+DIR_UNKNOWN = DEFINES['SNAKE_DIR_UNKNOWN']      # both bytes of a direction not known yet
 
 
 class _ObsPolicy:

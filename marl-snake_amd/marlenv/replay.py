@@ -16,10 +16,10 @@ that is neither 0 nor 1 comes back as 1.
 import ctypes
 
 from ._device import get_torch as _torch, stream_ptr
-from ._native import ReplayCfg, ReplayLayout, ReplayRings, check, lib
+from ._native import DEFINES, ReplayCfg, ReplayLayout, ReplayRings, check, lib
 from .pyrandom import PyRandom
 
-FORMATS = {'uint8': 0, 'float32': 1}
+FORMATS = {'uint8': DEFINES['SNAKE_REPLAY_U8_NHWC'], 'float32': DEFINES['SNAKE_REPLAY_F32_NCHW']}
 
 
 class ReplayBuffer:

@@ -5,6 +5,8 @@ reference's dfs_sweep_empty order (golden digests)."""
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -36,6 +38,109 @@ def test_exports_match_header(native):
     for n in names:
         assert hasattr(L, n), n
     assert L.snake_abi_version() == native.SNAKE_ABI_VERSION
+
+
+def test_struct_layouts_match_the_c_compiler(native, tmp_path):
+    """The Structures read from the header have the sizes and field offsets a C
+    compiler gives the header's own structs: one _Static_assert per struct and
+    per field."""
+    lines = ['#include <stddef.h>', '#include "snake_env.h"']
+    for name, T in native.HEADER.structs.items():
+        lines.append(f'_Static_assert(sizeof({name}) == {ctypes.sizeof(T)}, "sizeof {name}");')
+        lines += [f'_Static_assert(offsetof({name}, {f}) == {getattr(T, f).offset}, "{name}.{f}");'
+                  for f, _ in T._fields_]
+    assert len(native.HEADER.structs) >= 19 and len(lines) >= 2 + 190
+    src = tmp_path / 'layout.c'
+    src.write_text('\n'.join(lines) + '\n')
+    rocm_clang = os.path.join(os.environ.get('ROCM_PATH', '/opt/rocm'), 'lib', 'llvm', 'bin', 'clang')
+    cc = shutil.which('cc') or shutil.which('gcc') or shutil.which('clang') or rocm_clang
+    r = subprocess.run([cc, '-std=c11', '-fsyntax-only', '-I' + os.path.join(ROOT, 'include'), str(src)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
+def test_every_function_is_bound(native):
+    """Every prototype of the header, found by a regex of this test's own, is bound
+    on the loaded library with as many argtypes as the header has arguments and
+    the restype of its return type."""
+    src = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'snake_env.h')).read(), flags=re.S)
+    protos = re.findall(r'^(int|int64_t|const char \*)\s*(snake_\w+)\(([^)]*)\);', src, flags=re.M)
+    assert [n for _, n, _ in protos] == list(native.EXPORTS) and len(protos) == len(header_functions())
+    restypes = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'const char *': ctypes.c_char_p}
+    L = native.lib()
+    for ret, name, args in protos:
+        f = getattr(L, name)
+        assert len(f.argtypes) == (0 if args.strip() == 'void' else args.count(',') + 1), name
+        assert f.restype is restypes[ret], name
+    assert L.snake_step.argtypes[:2] == [ctypes.POINTER(native.SnakeCfg), ctypes.POINTER(native.SnakeState)]
+    # snake_genome_tile and snake_epi_stat are passed as raw addresses
+    assert L.snake_genome_actions.argtypes[2] is ctypes.c_void_p
+    assert dict(native.SnakeState._fields_)['stats'] is ctypes.c_void_p
+
+
+SHORT_HEADER = """\
+/* a comment; with { and ( in it */
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define SNAKE_TWO 2          // two; {
+#define SNAKE_NEG (-128)
+#define SNAKE_HEX 0x10
+#define SNAKE_GUARD
+typedef struct {
+    int32_t height, width;   /* both; in cells */
+    double  scale;
+    uint16_t fruits, kills;
+    const float *w, *b;      // pointers (two)
+    int64_t *count;
+} snake_a;
+typedef struct { snake_a *a; const snake_epi_stat *stats; uint8_t flag; } snake_b;
+int snake_f(const snake_a *a, int64_t n,
+            snake_b *out,   /* written; */
+            void *stream);
+int snake_void(void);
+int snake_ll(const char *name, long long value, float x, snake_epi_stat *s);
+const char *snake_text(void);
+int64_t snake_count(const int32_t *rows);
+#ifdef __cplusplus
+}
+#endif
+"""
+
+
+def test_header_parser():
+    from marlenv._header import Header
+    c = ctypes
+    h = Header('typedef struct { double score; } snake_epi_stat;\n' + SHORT_HEADER)
+    assert h.defines == {'SNAKE_TWO': 2, 'SNAKE_NEG': -128, 'SNAKE_HEX': 16}
+    A, B = h.structs['snake_a'], h.structs['snake_b']
+    assert A._fields_ == [('height', c.c_int32), ('width', c.c_int32), ('scale', c.c_double),
+                          ('fruits', c.c_uint16), ('kills', c.c_uint16), ('w', c.c_void_p), ('b', c.c_void_p),
+                          ('count', c.c_void_p)]
+    assert B._fields_ == [('a', c.POINTER(A)), ('stats', c.c_void_p), ('flag', c.c_uint8)]
+    assert list(h.functions) == ['snake_f', 'snake_void', 'snake_ll', 'snake_text', 'snake_count']
+    assert h.functions['snake_f'] == (c.c_int, [c.POINTER(A), c.c_int64, c.POINTER(B), c.c_void_p])
+    assert h.functions['snake_void'] == (c.c_int, [])
+    assert h.functions['snake_ll'] == (c.c_int, [c.c_char_p, c.c_longlong, c.c_float, c.c_void_p])
+    assert h.functions['snake_text'] == (c.c_char_p, [])
+    assert h.functions['snake_count'] == (c.c_int64, [c.c_void_p])
+
+
+@pytest.mark.parametrize('text,line,word', [
+    ('int snake_ok(void);\n\n/* two\n lines */ int snake_f(size_t n);\n', 4, 'size_t'),      # unknown type, argument
+    ('typedef struct {\n    int32_t a;\n    unsigned b;\n} snake_s;\n', 3, 'unsigned'),       # unknown type, field
+    ('snake_t snake_f(void);\n', 1, 'snake_t'),                                               # unknown type, return
+    ('typedef struct {\n    int32_t a\n} snake_s;\n', 2, 'int32_t a'),                        # no ';'
+    ('int snake_ok(void);\nint snake_f(int (*cb)(int));\n', 2, 'snake_f'),                    # not read
+    ('int snake_f(int32_t);\n', 1, 'int32_t'),                                                # an argument without a name
+    ('int snake_f(void x);\n', 1, 'void'),
+    ('#define SNAKE_OK 0\n#define SNAKE_X (1 << 3)\n', 2, 'SNAKE_X'),                        # a define that is no literal
+    ('#define SNAKE_MAX(a, b) 4\n', 1, 'SNAKE_MAX'),
+])
+def test_header_parser_names_the_line_it_cannot_read(text, line, word):
+    from marlenv._header import Header, HeaderError
+    with pytest.raises(HeaderError, match=rf'^line {line}: .*{word}'):
+        Header(text)
 
 
 def cfg(native, **kw):
