@@ -13,6 +13,9 @@
  *     owned by the caller (PyTorch); the library allocates nothing on the device.
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream); calls
  *     are stream-ordered and asynchronous; not re-entrant per state.
+ *   - every launch runs on the stream's device (NULL: the device current at the
+ *     call), whatever device the calling thread has current; that device is
+ *     current again on return.
  *   - return 0 on success, a negative SNAKE_E* code on a bad argument (message in
  *     snake_last_error()), never abort.
  *   - env i of a batch is a standalone reference SnakeEnv after
@@ -346,7 +349,8 @@ int snake_dqn_plan(const snake_dqn_cfg *cfg, snake_dqn_layout *out);
 int64_t snake_dqn_rows(const snake_dqn_cfg *cfg, int32_t *rows, int64_t n);
 
 /* q_out: float [B][A]; feat_out (may be NULL): float [B][128] = forward_features;
- * act_scratch: bf16 [B][act_per_obs] device buffer. Two launches on `stream`. */
+ * act_scratch: bf16 [B][act_per_obs] device buffer. Two launches on `stream`, on
+ * the stream's device. */
 int snake_dqn_forward(const snake_dqn_cfg *cfg, const snake_dqn_net *net, const uint8_t *obs,
                       int64_t batch, uint16_t *act_scratch, float *q_out, float *feat_out,
                       void *stream);
@@ -359,7 +363,8 @@ int snake_dqn_forward(const snake_dqn_cfg *cfg, const snake_dqn_net *net, const 
  * time and loops over the row tiles, so h and w are runtime values. Same
  * structs and argument lists as the three functions above, whose window path
  * (3x3 .. 11x11) stays the faster one where it applies. What the plan rejects
- * is SNAKE_E_CONFIG; larger maps take fp32 mode below. */
+ * is SNAKE_E_CONFIG; larger maps take fp32 mode below. The forward's two
+ * launches run on `stream`, on the stream's device. */
 int snake_dqn_map_plan(const snake_dqn_cfg *cfg, snake_dqn_layout *out);
 int64_t snake_dqn_map_rows(const snake_dqn_cfg *cfg, int32_t *rows, int64_t n);
 int snake_dqn_map_forward(const snake_dqn_cfg *cfg, const snake_dqn_net *net, const uint8_t *obs,
@@ -381,7 +386,8 @@ typedef struct {
 /* Device scratch bytes snake_dqn32_forward needs for `batch` observations (< 0 on error). */
 int64_t snake_dqn32_scratch(const snake_dqn_cfg *cfg, int64_t batch);
 
-/* q_out: float [B][A]; feat_out (may be NULL): float [B][128]. Seven launches on `stream`. */
+/* q_out: float [B][A]; feat_out (may be NULL): float [B][128]. Seven launches on
+ * `stream`, on the stream's device. */
 int snake_dqn32_forward(const snake_dqn_cfg *cfg, const snake_dqn32_net *net, const uint8_t *obs,
                         int64_t batch, void *scratch, float *q_out, float *feat_out, void *stream);
 
@@ -412,7 +418,8 @@ int snake_dqn32_forward(const snake_dqn_cfg *cfg, const snake_dqn32_net *net, co
  * the vector ALUs. Split M: the M = B*h*w (fc: B) rows of a weight or bias
  * gradient are cut into chunks of max(2048, ceil(M/128) rounded up to 16) rows;
  * with more than one chunk each writes a partial and a second kernel adds the
- * partials in chunk order. batch in [0, 2^24]. */
+ * partials in chunk order. batch in [0, 2^24]. Every launch on `stream`, on the
+ * stream's device. */
 int64_t snake_dqn32_train_scratch(const snake_dqn_cfg *cfg, int64_t batch);   /* bytes, < 0 on error */
 int snake_dqn32_backward(const snake_dqn_cfg *cfg, const snake_dqn32_net *net, const uint8_t *obs,
                          int64_t batch, const void *fwd_scratch, const float *dq, void *train_scratch,
@@ -439,7 +446,8 @@ int snake_dqn32_backward(const snake_dqn_cfg *cfg, const snake_dqn32_net *net, c
  *   fixed order that depends on the shape alone;
  *   fc3 (weight, bias and input gradient, so dY5) and the sums of the split-M
  *   partials: the fp32 function's kernels, bit-equal to it.
- * No floating-point atomics; results are bitwise reproducible. */
+ * No floating-point atomics; results are bitwise reproducible. Every launch on
+ * `stream`, on the stream's device. */
 int snake_dqn32_backward_bf16(const snake_dqn_cfg *cfg, const snake_dqn32_net *net, const uint8_t *obs,
                               int64_t batch, const void *fwd_scratch, const float *dq, void *train_scratch,
                               const snake_dqn32_net *grad, void *stream);
@@ -469,12 +477,14 @@ int snake_dqn32_backward_bf16(const snake_dqn_cfg *cfg, const snake_dqn32_net *n
  * one chunk each writes a partial [chunk][B][N] and a second kernel adds the
  * partials in chunk order. The rule depends on K alone: a row's results do not
  * depend on the batch it is in. No floating-point atomics; every summation
- * order is a function of the shape alone, results are bitwise reproducible. */
+ * order is a function of the shape alone, results are bitwise reproducible.
+ * Every launch on `stream`, on the stream's device. */
 int64_t snake_dqn32_forward_bf16_scratch(const snake_dqn_cfg *cfg, int64_t batch);   /* bytes, < 0 on error */
 int snake_dqn32_forward_bf16(const snake_dqn_cfg *cfg, const snake_dqn32_net *net, const uint8_t *obs,
                              int64_t batch, void *scratch, float *q_out, float *feat_out, void *stream);
 
-/* The TD loss (:243-250), one launch. Per row b, in fp32 and in this order:
+/* The TD loss (:243-250), one launch on `stream`, on the stream's device. Per
+ * row b, in fp32 and in this order:
  *   target = reward[b] + ((1 - done[b]) * gamma) * max_a next_q[b][a]
  *   d      = q[b][action[b]] - target
  * loss_out (one float) = (sum_b smooth_l1(d)) / B with smooth_l1(d) = 0.5 d^2
@@ -489,7 +499,7 @@ int snake_dqn_td_loss(const float *q, const int64_t *action, const float *reward
 /* clip_grad_norm_(params, max_norm) then optim.Adam.step() (torch defaults: no
  * amsgrad, no weight decay) over n elements; param, grad, exp_avg, exp_avg_sq
  * are flat float [n] device buffers (padding elements hold zero gradients and
- * stay unchanged). Three launches:
+ * stay unchanged). Three launches on `stream`, on the stream's device:
  *   norm  = sqrt(sum g^2)            two-stage, fixed order; also to *norm_out
  *   coef  = min(1, max_norm / (norm + 1e-6));  g' = g * coef  (grad is not written)
  *   m     = beta1 m + (1 - beta1) g';  v = beta2 v + ((1 - beta2) g') g'

@@ -393,7 +393,7 @@ int conv_mfma(const GemmArgs &g, hipStream_t s, const char *what)
     // 9.84 -> 9.75 ms; parity green)
     if constexpr (NT == 4) hipLaunchKernelGGL((k_conv32_mfma<MODE, 4, true>), grid, dim3(256), (size_t)lds, s, g);
     else hipLaunchKernelGGL((k_conv32_mfma<MODE, NT>), grid, dim3(256), (size_t)lds, s, g);
-    return launched(what);
+    return launch_status(what);
 }
 
 // The dense layers with N a multiple of 128 (fc1: 64hw -> 256, fc2: 256 -> 128)
@@ -594,7 +594,7 @@ int fc_mfma(const GemmArgs &g, hipStream_t s, const char *what)
         hipLaunchKernelGGL(k_fc32_mfma_small, dim3((unsigned)((g.M + 31) / 32), (unsigned)(g.N / 32)), dim3(256), 0, s, g);
     else
         hipLaunchKernelGGL(k_fc32_mfma, grid, dim3(512), 0, s, g);
-    return launched(what);
+    return launch_status(what);
 }
 
 // flag = any observation byte > 1 (the reference's x.max() > 1.0 test)
@@ -621,7 +621,7 @@ int gemm(const GemmArgs &g, hipStream_t s, const char *what)
 {
     const dim3 grid((unsigned)((g.M + BM - 1) / BM), (unsigned)((g.N + BN - 1) / BN));
     hipLaunchKernelGGL(k_gemm32<MODE>, grid, dim3(kThreads), 0, s, g);
-    return launched(what);
+    return launch_status(what);
 }
 
 }  // namespace dqn32
@@ -655,6 +655,8 @@ static int forward(const char *who, bool bf16, const snake_dqn_cfg *cfg, const s
     if (batch < 0) { set_error("%s: batch < 0", who); return SNAKE_E_ARG; }
     if (batch == 0) return SNAKE_OK;
     const hipStream_t s = (hipStream_t)stream;
+    DeviceGuard dg(s);
+    if (dg.dev < 0) return SNAKE_E_LAUNCH;
     dqn32::Scratch sc;
     float *partials = nullptr;
     if (bf16) dqn32::fwd16_scratch_bytes(cfg, batch, scratch, &sc, &partials);
@@ -666,7 +668,7 @@ static int forward(const char *who, bool bf16, const snake_dqn_cfg *cfg, const s
         const int64_t n = BP * C;
         const unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, 4096);
         hipLaunchKernelGGL(dqn32::k_obs_max, dim3(blocks), dim3(256), 0, s, obs, n, sc.flag);
-        if ((rc = launched("k_obs_max"))) return rc;
+        if ((rc = launch_status("k_obs_max"))) return rc;
     }
     dqn32::GemmArgs g{};
     g.H = H; g.W = W;
@@ -710,7 +712,7 @@ static int forward(const char *who, bool bf16, const snake_dqn_cfg *cfg, const s
         const int64_t total = batch * 128;
         hipLaunchKernelGGL(dqn32::k_bias_relu, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, sc.y5,
                            net->fc2_b, 128, total, feat_out);
-        if ((rc = launched("k_bias_relu"))) return rc;
+        if ((rc = launch_status("k_bias_relu"))) return rc;
     }
     return SNAKE_OK;
 }

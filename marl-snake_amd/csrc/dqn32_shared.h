@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "snake_internal.h"
+#include "snake_device.h"
 
 namespace snake {
 namespace dqn32 {

@@ -222,7 +222,7 @@ int gemm16(int mode, const GemmArgs &g, float *partials, hipStream_t s, const ch
         hipLaunchKernelGGL(k_fwd16<kConvF32>, grid, dim3(256), 0, s, g, chunk, part);
     else
         hipLaunchKernelGGL(k_fwd16<kConvU8>, grid, dim3(256), 0, s, g, chunk, part);
-    int rc = launched(what);
+    int rc = launch_status(what);
     if (!rc && chunks > 1) rc = train::reduce(part, part, chunks, g.M * g.N, 0, g.y, g.y, s, what);
     return rc;
 }

@@ -39,8 +39,14 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <map>
+#include <mutex>
+#include <set>
+#include <tuple>
+#include <utility>
 
 #include "snake_internal.h"
+#include "snake_device.h"
 
 namespace snake {
 namespace dqn {
@@ -806,7 +812,6 @@ struct ConvTable {
 const ConvTable<1> kConv1;
 const ConvTable<2> kConv2;
 const ConvTable<4> kConv4;
-int g_conv_grid[3][5][3];
 // waves per observation in k_dqn_conv when snake_dqn_cfg.conv_waves is 0: 4
 // (two for odd row-tile counts). Forward at 262144 observations: 4.51 / 4.57 /
 // 5.91 ms for 4 / 2 / 1 (conv_waves selects the others).
@@ -826,18 +831,39 @@ int check_forward(const char *who, const snake_dqn_net *net, const uint8_t *obs,
     return SNAKE_OK;
 }
 
-// persistent grid: the resident workgroups of the whole device (0, and the error set, where the query fails)
-int persistent_grid(const char *who, const void *kernel, int threads, int lds)
+// What a launch needs to know about its device, asked once each and kept for the
+// process under one lock: the persistent grid -- the resident workgroups of the
+// whole device -- by (device, kernel, threads, LDS bytes), and the kernels whose
+// LDS limit is raised to kMapMaxLds by (device, kernel). A grid that is held
+// was asked after its kernel's limit was raised, so a call that finds its grid
+// looks nothing else up. dev: the DeviceGuard's, current here.
+std::mutex g_launch_mu;
+std::map<std::tuple<int, const void *, int, int>, int> g_grids;
+std::set<std::pair<int, const void *>> g_big_lds;
+
+// big_lds: the launch may ask for more than the 64 KB it gets without the
+// raised limit. 0, and the error set, where the runtime refuses.
+int persistent_grid(const char *who, int dev, const void *kernel, int threads, int lds, bool big_lds = false)
 {
-    int per_cu = 0, dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+    std::lock_guard<std::mutex> lock(g_launch_mu);
+    const auto key = std::make_tuple(dev, kernel, threads, lds);
+    const auto held = g_grids.find(key);
+    if (held != g_grids.end()) return held->second;
+    if (big_lds && !g_big_lds.count({dev, kernel})) {
+        if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kMapMaxLds) != hipSuccess) {
+            set_error("%s: cannot raise the kernel's LDS limit to %d bytes", who, kMapMaxLds);
+            return 0;
+        }
+        g_big_lds.insert({dev, kernel});
+    }
+    int per_cu = 0, cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds) != hipSuccess ||
         per_cu < 1 || cus < 1) {
         set_error("%s: occupancy query failed", who);
         return 0;
     }
-    return per_cu * cus;
+    return g_grids[key] = per_cu * cus;
 }
 
 // the fc layers on the conv kernel's output (either plan's)
@@ -850,7 +876,7 @@ int launch_fc(const snake_dqn_cfg *cfg, const snake_dqn_layout &lay, const snake
     fa.w6 = net->fc3_w; fa.b6 = net->fc3_b; fa.q = q_out; fa.feat = feat_out;
     const unsigned gfc = (unsigned)((batch + kFcObs - 1) / kFcObs);
     hipLaunchKernelGGL(k_dqn_fc, dim3(gfc), dim3(512), 0, s, fa);
-    return launched("k_dqn_fc");
+    return launch_status("k_dqn_fc");
 }
 }  // namespace
 
@@ -923,25 +949,22 @@ extern "C" int snake_dqn_forward(const snake_dqn_cfg *cfg, const snake_dqn_net *
     const ConvKernel ck = want == 1 ? kConv1.k[vi][ci] : (want == 4 ? kConv4.k[vi][ci] : kConv2.k[vi][ci]);
     const conv_kernel_t kc = ck.k;
     const int nw = ck.nw;
-    int &grid = g_conv_grid[want == 1 ? 0 : (want == 2 ? 1 : 2)][vi][ci];
-    if (!grid && !(grid = persistent_grid("snake_dqn_forward", (const void *)kc, 64 * nw, 0))) return SNAKE_E_LAUNCH;
+    DeviceGuard dg(s);
+    if (dg.dev < 0) return SNAKE_E_LAUNCH;
+    const int grid = persistent_grid("snake_dqn_forward", dg.dev, (const void *)kc, 64 * nw, 0);
+    if (!grid) return SNAKE_E_LAUNCH;
     const unsigned gconv = (unsigned)std::min<int64_t>(batch, grid);
     hipLaunchKernelGGL(kc, dim3(gconv), dim3(64 * nw), 0, s, ca);
-    if ((rc = launched("k_dqn_conv"))) return rc;
+    if ((rc = launch_status("k_dqn_conv"))) return rc;
     return launch_fc(cfg, lay, net, batch, act_scratch, q_out, feat_out, s);
 }
 
 // ---- the map path's host side --------------------------------------------
 namespace {
 typedef void (*map_kernel_t)(MapArgs);
-struct MapKernel {
-    map_kernel_t k;
-    int lds, grid;      // the persistent grid at `lds` bytes of LDS per workgroup (0: not asked yet)
-    bool big_lds;       // the kernel may be launched with kMapMaxLds
-};
-MapKernel g_map[2][3] = {
-    {{k_dqn_map_conv<3, 8>, 0, 0, false}, {k_dqn_map_conv<4, 8>, 0, 0, false}, {k_dqn_map_conv<5, 8>, 0, 0, false}},
-    {{k_dqn_map_conv<3, 16>, 0, 0, false}, {k_dqn_map_conv<4, 16>, 0, 0, false}, {k_dqn_map_conv<5, 16>, 0, 0, false}},
+const map_kernel_t g_map[2][3] = {
+    {k_dqn_map_conv<3, 8>, k_dqn_map_conv<4, 8>, k_dqn_map_conv<5, 8>},
+    {k_dqn_map_conv<3, 16>, k_dqn_map_conv<4, 16>, k_dqn_map_conv<5, 16>},
 };
 // waves per observation in k_dqn_map_conv when snake_dqn_cfg.conv_waves is 0.
 // 16 384 observations of 20x20x8: the kernel takes 0.77 ms with 16 waves, 0.87 ms with 8.
@@ -1043,22 +1066,14 @@ extern "C" int snake_dqn_map_forward(const snake_dqn_cfg *cfg, const snake_dqn_n
         return SNAKE_E_CONFIG;
     }
     const int nw = cfg->conv_waves ? cfg->conv_waves : map_conv_waves();
-    MapKernel &mk = g_map[nw == 16][lay.cpad == 8 ? 0 : (lay.cpad == 16 ? 1 : 2)];
-    if (!mk.big_lds) {   // more than the 64 KB a launch may ask for without it
-        if (hipFuncSetAttribute((const void *)mk.k, hipFuncAttributeMaxDynamicSharedMemorySize, kMapMaxLds) != hipSuccess) {
-            set_error("snake_dqn_map_forward: cannot raise the kernel's LDS limit to %d bytes", kMapMaxLds);
-            return SNAKE_E_LAUNCH;
-        }
-        mk.big_lds = true;
-    }
-    if (mk.lds != lay.lds_conv) {   // the grid depends on the LDS a workgroup takes
-        const int grid = persistent_grid("snake_dqn_map_forward", (const void *)mk.k, 64 * nw, lay.lds_conv);
-        if (!grid) return SNAKE_E_LAUNCH;
-        mk.grid = grid;
-        mk.lds = lay.lds_conv;
-    }
-    const unsigned gconv = (unsigned)std::min<int64_t>(batch, mk.grid);
-    hipLaunchKernelGGL(mk.k, dim3(gconv), dim3(64 * nw), lay.lds_conv, s, ma);
-    if ((rc = launched("k_dqn_map_conv"))) return rc;
+    const map_kernel_t mk = g_map[nw == 16][lay.cpad == 8 ? 0 : (lay.cpad == 16 ? 1 : 2)];
+    DeviceGuard dg(s);
+    if (dg.dev < 0) return SNAKE_E_LAUNCH;
+    // the grid depends on the LDS a workgroup takes
+    const int grid = persistent_grid("snake_dqn_map_forward", dg.dev, (const void *)mk, 64 * nw, lay.lds_conv, true);
+    if (!grid) return SNAKE_E_LAUNCH;
+    const unsigned gconv = (unsigned)std::min<int64_t>(batch, grid);
+    hipLaunchKernelGGL(mk, dim3(gconv), dim3(64 * nw), lay.lds_conv, s, ma);
+    if ((rc = launch_status("k_dqn_map_conv"))) return rc;
     return launch_fc(cfg, lay, net, batch, act_scratch, q_out, feat_out, s);
 }

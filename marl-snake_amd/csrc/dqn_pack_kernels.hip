@@ -42,6 +42,7 @@
 #include <string.h>
 
 #include "snake_internal.h"
+#include "snake_device.h"
 
 namespace snake {
 namespace pack {
@@ -253,8 +254,10 @@ extern "C" int snake_dqn_pack32(const snake_dqn_cfg *cfg, int32_t map_plan, cons
     int small = a.end_fc2;
     for (int i = 0; i < kCopies; i++) small += a.cnum[i];
     const unsigned grid = (unsigned)(a.fc1_blocks + (small + 255) / 256);
+    DeviceGuard dg((hipStream_t)stream);
+    if (dg.dev < 0) return SNAKE_E_LAUNCH;
     hipLaunchKernelGGL(k_dqn_pack, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-    return launched("k_dqn_pack");
+    return launch_status("k_dqn_pack");
 }
 
 extern "C" int snake_dqn_pack32_host(const snake_dqn_cfg *cfg, int32_t map_plan, const snake_dqn32_net *src,

@@ -360,7 +360,7 @@ int wgrad16(int mode, WgradArgs g, float *grad_w, float *grad_b, const TrainScra
         hipLaunchKernelGGL(k_wgrad16<kConvF32>, grid, dim3(256), 0, s, g);
     else
         hipLaunchKernelGGL(k_wgrad16<kConvU8>, grid, dim3(256), 0, s, g);
-    int rc = launched(what);
+    int rc = launch_status(what);
     if (!rc && chunks > 1) rc = reduce(ts.wpart, ts.bpart, chunks, (int64_t)g.N * g.K, g.N, grad_w, grad_b, s, what);
     return rc;
 }
@@ -374,7 +374,7 @@ int dgrad16(bool conv, const DgradArgs &g, hipStream_t s, const char *what)
     } else {
         hipLaunchKernelGGL(k_dgrad16<false>, grid, dim3(256), 0, s, g);
     }
-    return launched(what);
+    return launch_status(what);
 }
 
 }  // namespace train

@@ -493,7 +493,7 @@ int reduce(const float *wpart, const float *bpart, int64_t chunks, int64_t nw, i
 {
     hipLaunchKernelGGL(k_reduce, dim3((unsigned)((nw + nb + 255) / 256)), dim3(256), 0, s, wpart, bpart, (int)chunks,
                        nw, nb, wout, bout);
-    return launched(what);
+    return launch_status(what);
 }
 
 // a layer's weight and bias gradient
@@ -506,7 +506,7 @@ int wgrad(WgradArgs g, float *grad_w, float *grad_b, const TrainScratch &ts, hip
     g.bout = chunks > 1 ? ts.bpart : grad_b;
     const dim3 grid((unsigned)((g.K + kT - 1) / kT), (unsigned)((g.N + kT - 1) / kT), (unsigned)chunks);
     hipLaunchKernelGGL(k_wgrad<MODE>, grid, dim3(256), 0, s, g);
-    int rc = launched(what);
+    int rc = launch_status(what);
     if (!rc && chunks > 1) rc = reduce(ts.wpart, ts.bpart, chunks, (int64_t)g.N * g.K, g.N, grad_w, grad_b, s, what);
     return rc;
 }
@@ -516,7 +516,7 @@ int colsum(const float *dy, int64_t M, int N, float *grad, float *bpart, hipStre
     const int64_t chunks = num_chunks(M);
     hipLaunchKernelGGL(k_colsum, dim3((unsigned)chunks), dim3(256), 0, s, dy, M, N, chunk_rows(M),
                        chunks > 1 ? bpart : grad);
-    int rc = launched(what);
+    int rc = launch_status(what);
     if (!rc && chunks > 1) rc = reduce(bpart, bpart, chunks, N, 0, grad, grad, s, what);
     return rc;
 }
@@ -526,7 +526,7 @@ int dgrad(const DgradArgs &g, hipStream_t s, const char *what)
 {
     const dim3 grid((unsigned)((g.M + kT - 1) / kT), (unsigned)((g.K + kT - 1) / kT));
     hipLaunchKernelGGL(k_dgrad<CONV>, grid, dim3(256), 0, s, g);
-    return launched(what);
+    return launch_status(what);
 }
 
 int check_train(const snake_dqn_cfg *cfg, int64_t batch, const char *who)
@@ -590,6 +590,8 @@ static int backward(const char *who, bool bf16, const snake_dqn_cfg *cfg, const 
     }
     if (batch == 0) return SNAKE_OK;
     const hipStream_t s = (hipStream_t)stream;
+    DeviceGuard guard(s);       // (dg is the input gradient's argument block below)
+    if (guard.dev < 0) return SNAKE_E_LAUNCH;
     dqn32::Scratch fw;
     dqn32::scratch_bytes(cfg, batch, const_cast<void *>(fwd_scratch), &fw);
     train::TrainScratch ts;
@@ -601,14 +603,14 @@ static int backward(const char *who, bool bf16, const snake_dqn_cfg *cfg, const 
         const int64_t chunks = train::num_chunks(batch);
         hipLaunchKernelGGL(train::k_fc3_wgrad, dim3((unsigned)chunks, (unsigned)A), dim3(1024), 0, s, dq, fw.y5,
                            net->fc2_b, batch, A, train::chunk_rows(batch), chunks > 1 ? ts.wpart : grad->fc3_w);
-        if ((rc = launched("fc3 weight gradient"))) return rc;
+        if ((rc = launch_status("fc3 weight gradient"))) return rc;
         if (chunks > 1 && (rc = train::reduce(ts.wpart, ts.wpart, chunks, (int64_t)A * 128, 0, grad->fc3_w,
                                               grad->fc3_w, s, "fc3 weight gradient")))
             return rc;
         if ((rc = train::colsum(dq, batch, A, grad->fc3_b, ts.bpart, s, "fc3 bias gradient"))) return rc;
         hipLaunchKernelGGL(train::k_fc3_dgrad, dim3((unsigned)((batch * 128 + 255) / 256)), dim3(256), 0, s, dq,
                            net->fc3_w, fw.y5, net->fc2_b, batch, A, ts.dy5);
-        if ((rc = launched("fc3 input gradient"))) return rc;
+        if ((rc = launch_status("fc3 input gradient"))) return rc;
     }
     auto wgrad = [&](int mode, const train::WgradArgs &g, float *gw, float *gb, const train::TrainScratch &t,
                      hipStream_t st, const char *what) {
@@ -687,9 +689,11 @@ extern "C" int snake_dqn_td_loss(const float *q, const int64_t *action, const fl
         set_error("snake_dqn_td_loss: num_actions must be in [1, 64] (got %d)", num_actions);
         return SNAKE_E_CONFIG;
     }
+    DeviceGuard dg((hipStream_t)stream);
+    if (dg.dev < 0) return SNAKE_E_LAUNCH;
     hipLaunchKernelGGL(train::k_td_loss, dim3(1), dim3(256), 0, (hipStream_t)stream, q, action, reward, done, next_q,
                        batch, num_actions, gamma, loss_out, dq, err);
-    return launched("k_td_loss");
+    return launch_status("k_td_loss");
 }
 
 extern "C" int snake_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
@@ -708,18 +712,20 @@ extern "C" int snake_adam_step(float *param, const float *grad, float *exp_avg, 
     }
     if (!(max_norm > 0.f)) { set_error("snake_adam_step: max_norm must be positive"); return SNAKE_E_CONFIG; }
     const hipStream_t s = (hipStream_t)stream;
+    DeviceGuard dg(s);
+    if (dg.dev < 0) return SNAKE_E_LAUNCH;
     float *sc = reinterpret_cast<float *>(scratch);
     const int G = (int)std::min<int64_t>(train::kNormBlocks, (n + 1023) / 1024);
     const int64_t L = ((n + G - 1) / G + 255) / 256 * 256;
     hipLaunchKernelGGL(train::k_sumsq, dim3(G), dim3(256), 0, s, grad, n, L, sc);
-    int rc = launched("k_sumsq");
+    int rc = launch_status("k_sumsq");
     if (rc) return rc;
     hipLaunchKernelGGL(train::k_norm, dim3(1), dim3(256), 0, s, sc, G, norm_out);
-    if ((rc = launched("k_norm"))) return rc;
+    if ((rc = launch_status("k_norm"))) return rc;
     // the bias corrections in double from the fp32 betas, as torch's Python scalars
     const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
     const float step_size = (float)((double)lr / bc1), bc2_sqrt = (float)sqrt(bc2);
     hipLaunchKernelGGL(train::k_adam, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, param, grad, exp_avg,
                        exp_avg_sq, n, sc + train::kNormBlocks, max_norm, beta1, beta2, step_size, bc2_sqrt, eps);
-    return launched("k_adam");
+    return launch_status("k_adam");
 }

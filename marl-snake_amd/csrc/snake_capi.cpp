@@ -46,13 +46,6 @@ void set_error(const char *fmt, ...)
     va_end(ap);
 }
 
-int launched(const char *what)
-{
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) { set_error("%s launch failed: %s", what, hipGetErrorString(err)); return SNAKE_E_LAUNCH; }
-    return SNAKE_OK;
-}
-
 static int pow2_at_least(int x)
 {
     int p = 1;

@@ -1,14 +1,16 @@
-// snake_device.h -- DeviceGuard, shared by the launchers of snake_kernels.hip
-// (snake_launch.inc) and of the policy, greedy, genome and replay kernels, and
-// the launch status the last four report. Include after <hip/hip_runtime.h> and
-// snake_internal.h.
+// snake_device.h -- the library's one device rule and its one launch status,
+// shared by every launcher: snake_kernels.hip (snake_launch.inc), the policy,
+// greedy, graph, genome, replay and pyrandom kernels and the DQN family.
+// Include after <hip/hip_runtime.h> and snake_internal.h.
 #pragma once
 
 namespace snake {
 
-// Every launch runs with the caller stream's device current: the side stream and
-// events are created on it, and a SnakeVecEnv on cuda:1 works whatever device the
-// calling thread has current (restored on return).
+// Every launch runs with the caller stream's device current (a null stream: the
+// device that is current already): the side stream and events are created on
+// it, what a launcher caches per device is keyed by `dev`, and an object on
+// cuda:1 works whatever device the calling thread has current (restored on
+// return). dev < 0, and the error set, where the runtime refuses.
 struct DeviceGuard {
     int dev = -1, prev = -1;
     explicit DeviceGuard(hipStream_t s)

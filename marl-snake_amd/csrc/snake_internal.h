@@ -186,8 +186,6 @@ constexpr FusedArea fused_area(int64_t N)
 }
 
 void set_error(const char *fmt, ...);
-// after a kernel launch: SNAKE_OK, or SNAKE_E_LAUNCH and the error "<what> launch failed: <the runtime's message>"
-int launched(const char *what);
 
 // launchers (snake_kernels.hip)
 int launch_seed(const KCfg &k, const snake_state &st, uint32_t base_seed, int64_t env_offset,

@@ -77,7 +77,7 @@ struct TimedLaunch {
         if (!a) return;
         t_ev0 = t_ev1 = nullptr;
         std::lock_guard<std::mutex> g(g_tmu);
-        // (a failed launch records neither: check_launch reports it, the pair
+        // (a failed launch records neither: launch_status reports it, the pair
         // goes back to the pool)
         if (hipPeekAtLastError() == hipSuccess) g_pending.push_back({name, a, b});
         else {
@@ -90,16 +90,7 @@ struct TimedLaunch {
 };
 
 // ---------------------------------------------------------------- launchers
-// (each under a DeviceGuard, snake_device.h)
-static int check_launch(const char *what)
-{
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        set_error("%s launch failed: %s", what, hipGetErrorString(err));
-        return SNAKE_E_LAUNCH;
-    }
-    return SNAKE_OK;
-}
+// (each under a DeviceGuard and checked by launch_status, snake_device.h)
 
 // The background stream's events only order kernels of one device: no
 // system-scope fence (that would write the L2s back for a host that never looks).
@@ -207,7 +198,7 @@ int launch_seed(const KCfg &k, const snake_state &st, uint32_t base_seed, int64_
     if (dg.dev < 0) return SNAKE_E_LAUNCH;
     if (int rc = wait_background(st, stream)) return rc;
     slaunch(k_seed, dim3(blocks), dim3(threads), 0, (hipStream_t)stream, k, st, base_seed, (long long)env_offset);
-    return check_launch("k_seed");
+    return launch_status("k_seed");
 }
 
 int launch_render(const KCfg &k, const snake_state &st, const uint8_t *palette, uint8_t *rgb, void *stream)
@@ -220,7 +211,7 @@ int launch_render(const KCfg &k, const snake_state &st, const uint8_t *palette, 
     const int threads = 256;
     const long long blocks = (quads + threads - 1) / threads;
     slaunch(k_render, dim3((unsigned)blocks), dim3(threads), 0, (hipStream_t)stream, k, st, pal, rgb);
-    return check_launch("k_render");
+    return launch_status("k_render");
 }
 
 // pick<V...>(v, f): f(Int<X>{}) for the X of V... that equals v -- the last of the list when none
@@ -250,7 +241,7 @@ int launch_reset(const KCfg &k, const snake_state &st, const uint8_t *mask, cons
         });
     });
     tl.close();
-    return check_launch("k_reset");
+    return launch_status("k_reset");
 }
 
 // The launch shape of the step's shared phase. k_post: the workers, then the encodes; npf (its NPF)
@@ -305,7 +296,7 @@ static int launch_encode(const KCfg &k, const snake_state &st, const snake_out &
     TimedLaunch t3("k_encode", sm);
     slaunch(k_encode, dim3(k.N), dim3(kWave), k.lds_obs_bytes, sm, k, st, o);
     t3.close();
-    return check_launch("k_encode");
+    return launch_status("k_encode");
 }
 
 // The whole step as one launch (k_step), on the state's next epoch.
@@ -336,7 +327,7 @@ static int launch_fused(KCfg &k, const snake_state &st, const int8_t *actions, c
         });
     });
     tf.close();
-    if (int rc = check_launch("k_step")) return rc;
+    if (int rc = launch_status("k_step")) return rc;
     std::lock_guard<std::mutex> g(g_bgmu);
     g_fu[st.env] = ep + 1;
     return SNAKE_OK;
@@ -370,7 +361,7 @@ static int launch_logic(const KCfg &k, const snake_state &st, const int8_t *acti
     });
     if (bgc && fork_ev == bgc->fork) t_ev1 = nullptr;
     t1.close();
-    return check_launch("k_logic");
+    return launch_status("k_logic");
 }
 
 // After k_logic has filled this step's queue set, a failure zeroes its
@@ -412,7 +403,7 @@ static int launch_spawn(const KCfg &k, const snake_state &st, const snake_out &o
         slaunch(k_spawn<PICKED(ms)>, dim3(k.spawn_slots), dim3(kWave), lds_sp, bx, sa);
     });
     t4.close();
-    if (int rc = check_launch("k_spawn")) return step_fail(k, st, bgc, false, sm, rc);
+    if (int rc = launch_status("k_spawn")) return step_fail(k, st, bgc, false, sm, rc);
     // (counted as soon as it is launched: its last worker adds one to the
     // set's finished count whatever fails after this point)
     bgc->launched[k.qpar]++;
@@ -467,7 +458,7 @@ int launch_step(const KCfg &k0, const snake_state &st, const int8_t *actions, co
             });
         });
         t2.close();
-        if ((rc = check_launch("k_autoreset"))) return step_fail(k, st, bgc, false, sm, rc);
+        if ((rc = launch_status("k_autoreset"))) return step_fail(k, st, bgc, false, sm, rc);
         return launch_encode(k, st, o, sm);
     }
     if (!k.autoreset) return launch_encode(k, st, o, sm);
@@ -477,7 +468,7 @@ int launch_step(const KCfg &k0, const snake_state &st, const int8_t *actions, co
     TimedLaunch t2("k_post", sm);
     launch_post(a, shape, k.bg != 0, link_record(k), sm);
     t2.close();
-    if ((rc = check_launch("k_post"))) return step_fail(k, st, bgc, bgc != nullptr, sm, rc);
+    if ((rc = launch_status("k_post"))) return step_fail(k, st, bgc, bgc != nullptr, sm, rc);
 #ifdef SNAKE_DIAG_ENC2
     // Diagnostic timing build: k_post once more with idle workers (aux set), so
     // the encodes alone are timed ("k_encode") with the same launch shape, LDS

@@ -24,7 +24,7 @@ independent model of them, written with torch ops, is tests/dqn_pack_ref.py.
 """
 import ctypes
 
-from ._device import get_torch, ptr, stream_ptr
+from ._device import check_tensor, default_device, get_torch, ptr, stream_ptr
 from ._native import DqnCfg, DqnLayout, DqnNet, check, lib
 from .dqn_weights import FIELDS, Net32, check_shapes
 
@@ -159,8 +159,10 @@ class DQNForward:
 
     @staticmethod
     def _device_of(device):
-        torch = get_torch()
-        return torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        """'cpu' (the host pack) as it is; any other by the package's rule, now."""
+        if device is not None and get_torch().device(device).type == 'cpu':
+            return get_torch().device(device)
+        return default_device(device, 'DQNForward')
 
     def _alloc(self, device, plan):
         """The bf16 side of both constructors: the plan (ValueError before any
@@ -207,11 +209,10 @@ class DQNForward:
 
     def _run(self, obs, features):
         H, W, C = self.cfg.height, self.cfg.width, self.cfg.channels
+        check_tensor('DQNForward', 'the env observations', obs, 'uint8')
         if obs.dim() == 3:
             obs = obs.unsqueeze(0)
         obs = obs.reshape(-1, H, W, C)
-        if obs.dtype != get_torch().uint8:
-            raise TypeError('DQNForward takes the env observations as uint8 (got %s)' % obs.dtype)
         obs = obs.to(self.device).contiguous()
         B = obs.shape[0]
         # bytes: the fp32 forward's own count, or the conv output as bf16 words

@@ -19,7 +19,7 @@ import ctypes
 import numpy as np
 
 from . import spaces
-from ._device import get_torch as _torch, ptr, stream_ptr
+from ._device import get_torch as _torch, check_on, check_tensor, ptr, stream_ptr
 from ._native import GraphCfg, check, lib
 from .vec_env import SnakeVecEnv
 
@@ -79,13 +79,9 @@ class GraphObs:
             obs = env.latest_obs()
             if obs is None:
                 raise ValueError('GraphObs: the env has no observation that is still alive; pass obs')
-        if obs.dtype != torch.uint8 or not obs.is_contiguous():
-            raise TypeError('GraphObs takes the observations as a contiguous uint8 tensor')
         N = env.num_envs
-        if tuple(obs.shape) != (N,) + self.obs_shape:
-            raise ValueError('obs shape %s is not %s' % (tuple(obs.shape), (N,) + self.obs_shape))
-        if obs.device != env.device:
-            raise ValueError('obs is on %s, the env on %s; there is no CPU fallback' % (obs.device, env.device))
+        check_tensor('GraphObs', 'obs', obs, 'uint8', (N,) + self.obs_shape, contiguous=True)
+        check_on('obs', obs, env.device, 'GraphObs')
         out = torch.empty((N,) + self.out_shape, dtype=self.dtype, device=env.device)
         with torch.cuda.device(env.device):
             check(self._L.snake_graph_obs(ctypes.byref(self.cfg), ptr(obs), ptr(env.snake), ptr(out), N,

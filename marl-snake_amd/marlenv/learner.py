@@ -28,7 +28,7 @@ weights after every step, one launch, no host sync.
 import ctypes
 import weakref
 
-from ._device import get_torch as _torch, ptr, stream_ptr
+from ._device import get_torch as _torch, check_on, check_tensor, default_device, ptr, stream_ptr
 from ._native import ADAM_SCRATCH_BYTES, DqnCfg, check, lib
 from .dqn import DQNForward, bf16_plan, forward32, forward32_bf16
 from .dqn_weights import FIELDS, NAMES, Net32, check_shapes, from_kernel, kernel_shapes, to_kernel  # noqa: F401
@@ -115,12 +115,7 @@ class DQNLearner:
         self.max_grad_norm = float(max_grad_norm)
         self.obs_shape = (H, W, C)
         self.num_actions = A
-        if not torch.cuda.is_available():
-            raise RuntimeError('DQNLearner needs a HIP device (MI355X); there is no CPU fallback')
-        dev = torch.device(device) if device is not None else torch.device('cuda')
-        if dev.index is None:
-            dev = torch.device('cuda', torch.cuda.current_device())
-        self.device = dev
+        self.device = dev = default_device(device, 'DQNLearner')
         # policy, target, gradient and Adam's m and v; and their flat buffers, which
         # the Adam kernel and the target sync take whole
         nets = self._pnet, self._tnet, self._gnet, self._mnet, self._vnet = [Net32(H * W, C, A, dev) for _ in range(5)]
@@ -148,13 +143,8 @@ class DQNLearner:
 
     # ----------------------------------------------------------------- forward
     def _check_obs(self, obs, who):
-        torch = _torch()
-        if not isinstance(obs, torch.Tensor) or obs.dtype != torch.uint8 or not obs.is_contiguous():
-            raise TypeError('DQNLearner.%s takes the observations as a contiguous uint8 tensor' % who)
-        if obs.dim() != 4 or tuple(obs.shape[1:]) != self.obs_shape:
-            raise ValueError('observations shape %s is not (B,) + %s' % (tuple(obs.shape), self.obs_shape))
-        if obs.device != self.device:
-            raise ValueError('observations are on %s, this DQNLearner on %s' % (obs.device, self.device))
+        check_tensor('DQNLearner.' + who, 'observations', obs, 'uint8', (None,) + self.obs_shape, contiguous=True)
+        check_on('observations', obs, self.device, 'DQNLearner')
         return obs.shape[0]
 
     def _forward(self, net, key, obs, features, who):
@@ -212,23 +202,15 @@ class DQNLearner:
         and sets self.err."""
         torch = _torch()
         A = self.num_actions
-        if not isinstance(q, torch.Tensor) or q.dtype != torch.float32:
-            raise TypeError('DQNLearner.td_loss takes q as a float32 tensor (got %s)' % getattr(q, 'dtype', type(q)))
-        if q.dim() != 2 or q.shape[1] != A:
-            raise ValueError('q shape %s is not (B, %d)' % (tuple(q.shape), A))
+        check_tensor('DQNLearner.td_loss', 'q', q, 'float32', (None, A))
         B = q.shape[0]
         if B < 1:
             raise ValueError('td_loss needs at least one row')
-        for name, t, dtype, shape in (('action', action, torch.int64, (B,)), ('reward', reward, torch.float32, (B,)),
-                                      ('done', done, torch.float32, (B,)), ('next_q', next_q, torch.float32, (B, A))):
-            if not isinstance(t, torch.Tensor) or t.dtype != dtype:
-                raise TypeError('DQNLearner.td_loss takes %s as a %s tensor (got %s)' % (
-                    name, dtype, getattr(t, 'dtype', type(t))))
-            if tuple(t.shape) != shape:
-                raise ValueError('%s shape %s is not %s' % (name, tuple(t.shape), shape))
+        for name, t, dtype, shape in (('action', action, 'int64', (B,)), ('reward', reward, 'float32', (B,)),
+                                      ('done', done, 'float32', (B,)), ('next_q', next_q, 'float32', (B, A))):
+            check_tensor('DQNLearner.td_loss', name, t, dtype, shape)
         for name, t in (('q', q), ('action', action), ('reward', reward), ('done', done), ('next_q', next_q)):
-            if t.device != self.device:
-                raise ValueError('%s is on %s, this DQNLearner on %s' % (name, t.device, self.device))
+            check_on(name, t, self.device, 'DQNLearner')
         q, action, reward, done, next_q = (t.contiguous() for t in (q, action, reward, done, next_q))
         loss = torch.empty((), dtype=torch.float32, device=self.device)
         dq = torch.empty((B, A), dtype=torch.float32, device=self.device)
@@ -242,21 +224,16 @@ class DQNLearner:
     def backward(self, obs, dq):
         """The gradients of sum(dq * Q(obs)) into the gradient buffer. obs must be
         the tensor of the last policy forward (its scratch is what is read)."""
-        torch = _torch()
         B = self._check_obs(obs, 'backward')
         if self._fwd is None or self._fwd[0] is not obs or self._fwd[1] != B:
             raise ValueError('backward needs the observations of the last policy forward (call learner(obs) first)')
-        if not isinstance(dq, torch.Tensor) or dq.dtype != torch.float32:
-            raise TypeError('DQNLearner.backward takes dq as a float32 tensor')
-        if tuple(dq.shape) != (B, self.num_actions):
-            raise ValueError('dq shape %s is not %s' % (tuple(dq.shape), (B, self.num_actions)))
-        if dq.device != self.device:
-            raise ValueError('dq is on %s, this DQNLearner on %s' % (dq.device, self.device))
+        check_tensor('DQNLearner.backward', 'dq', dq, 'float32', (B, self.num_actions))
+        check_on('dq', dq, self.device, 'DQNLearner')
         dq = dq.contiguous()
         need = int(self._L.snake_dqn32_train_scratch(ctypes.byref(self.cfg), B))
         check(need if need < 0 else 0, self._L)
         ts = self._buffer('train', need)
-        with torch.cuda.device(self.device):
+        with _torch().cuda.device(self.device):
             fn = self._L.snake_dqn32_backward_bf16 if self.backward_precision == 'bf16' \
                 else self._L.snake_dqn32_backward
             check(fn(ctypes.byref(self.cfg), ctypes.byref(self._pnet.struct), ptr(obs), B, ptr(self._scratch['policy']),

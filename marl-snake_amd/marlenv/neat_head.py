@@ -18,7 +18,7 @@ import ctypes
 
 import numpy as np
 
-from ._device import get_torch as _torch, bind_device, ptr, skip_mask, stream_ptr
+from ._device import get_torch as _torch, bind_device, check_tensor, ptr, skip_mask, stream_ptr
 from ._native import DEFINES, GenomeCfg, GenomeLayout, GenomeProg, GenomeTile, check, lib
 
 RELU, SIGMOID, TANH = (DEFINES['SNAKE_GENOME_' + n] for n in ('RELU', 'SIGMOID', 'TANH'))
@@ -197,8 +197,7 @@ class GenomeHeads:
         also the networks' outputs, float64 (N, S, A)."""
         torch = _torch()
         N, I, A = self.num_envs, self.num_inputs, self.num_outputs
-        if not isinstance(features, torch.Tensor) or features.dtype != torch.float32:
-            raise TypeError('GenomeHeads takes the features as a float32 tensor')
+        check_tensor('GenomeHeads', 'features', features, 'float32')
         if features.shape[-1] != I or features.numel() % (N * I) or features.numel() == 0:
             raise ValueError('features shape %s is not (%d * S, %d)' % (tuple(features.shape), N, I))
         S = features.numel() // (N * I)

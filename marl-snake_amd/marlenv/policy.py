@@ -12,7 +12,7 @@ DQN_Evaluator.evaluate.
 """
 import ctypes
 
-from ._device import get_torch as _torch, bind_device, ptr, skip_mask, stream_ptr
+from ._device import get_torch as _torch, bind_device, check_tensor, ptr, skip_mask, stream_ptr
 from ._native import DEFINES, PolicyCfg, check, lib
 
 DIR_UNKNOWN = DEFINES['SNAKE_DIR_UNKNOWN']      # both bytes of a direction not known yet
@@ -35,12 +35,7 @@ class _ObsPolicy:
 
     def _batch(self, obs):
         """(device, N) of an observation batch; binds this object to its device."""
-        torch = _torch()
-        name = type(self).__name__
-        if obs.dtype != torch.uint8 or not obs.is_contiguous():
-            raise TypeError('%s takes the observations as a contiguous uint8 tensor' % name)
-        if obs.dim() != 5 or tuple(obs.shape[1:]) != self.obs_shape:
-            raise ValueError('obs shape %s is not (N,) + %s' % (tuple(obs.shape), self.obs_shape))
+        check_tensor(type(self).__name__, 'obs', obs, 'uint8', (None,) + self.obs_shape, contiguous=True)
         bind_device(self, obs.device, 'observations', 'obs is')
         return obs.device, obs.shape[0]
 
@@ -88,8 +83,7 @@ class SafeActions(_ObsPolicy):
         torch = _torch()
         S = self.obs_shape[0]
         dev, N = self._batch(obs)
-        if q.dtype != torch.float32:
-            raise TypeError('SafeActions takes the Q-values as float32 (got %s)' % q.dtype)
+        check_tensor('SafeActions', 'q', q, 'float32')
         if tuple(q.shape) not in ((N, S, 3), (N * S, 3)):
             raise ValueError('q shape %s is neither (%d, %d, 3) nor (%d, 3)' % (tuple(q.shape), N, S, N * S))
         q = q.to(dev).contiguous()

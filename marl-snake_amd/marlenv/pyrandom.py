@@ -12,7 +12,7 @@ the stdlib's. Seeding happens on the host through `random.Random(seed)` itself.
 """
 import random
 
-from ._device import get_torch as _torch, ptr, stream_ptr
+from ._device import get_torch as _torch, bind_device, ptr, stream_ptr
 from ._native import check, lib
 
 MT_N = 624
@@ -53,27 +53,20 @@ class PyRandom:
         self.key = self.pos = self.err = None
 
     # ---------------------------------------------------------------- buffers
-    def _on(self, dev=None):
-        """The device arrays, created on `dev` at the first use."""
+    def _on(self, t, name):
+        """Binds the streams to the device of tensor `name` and, at the first
+        use, creates the device arrays there."""
         torch = _torch()
+        bind_device(self, t.device, name, name + ' is')
+        dev = self.device
         if self.key is None:
-            if self.device is not None and self.device.index is not None:
-                dev = self.device
-            elif dev is None:
-                if not torch.cuda.is_available():
-                    raise RuntimeError('PyRandom needs a HIP device (MI355X); there is no CPU fallback')
-                dev = torch.device('cuda', torch.cuda.current_device())
-            if dev.type != 'cuda':
-                raise ValueError('PyRandom needs the GPU (got %s); there is no CPU fallback' % (dev,))
             import numpy as np
             words = np.array([st[1] for st in self._host], dtype=np.uint32)
             self.key = torch.from_numpy(words[:, :MT_N].copy().view(np.int32)).to(dev)
             self.pos = torch.from_numpy(words[:, MT_N].astype(np.int32)).to(dev)
             self.err = torch.zeros(1, dtype=torch.int32, device=dev)
-            self.device, self._host = dev, None
-        elif dev is not None and dev != self.device:
-            raise ValueError('this PyRandom is on %s, not on %s' % (self.device, dev))
-        return self.device
+            self._host = None
+        return dev
 
     def getstate(self, i=0):
         """Stream i as a tuple that random.Random().setstate accepts. Syncs."""
@@ -101,7 +94,7 @@ class PyRandom:
         if N > self.n:
             raise ValueError('%d envs need %d streams, this PyRandom has %d' % (N, N, self.n))
         check(self._L.snake_pyrandom_plan(A, 1, 1), self._L)
-        dev = self._on(q.device)
+        dev = self._on(q, 'q')
         q = q.to(torch.float32).contiguous()
         if skip is not None:
             if tuple(skip.shape) != (N, S) or skip.device != dev:
@@ -124,7 +117,7 @@ class PyRandom:
         if not 0 <= stream < self.n:
             raise ValueError('stream must be in [0, %d) (got %d)' % (self.n, stream))
         check(self._L.snake_pyrandom_plan(1, B, int(capacity)), self._L)
-        dev = self._on(count.device)
+        dev = self._on(count, 'count')
         if count.dtype != torch.int64 or count.numel() != 1:
             raise TypeError('count must be one int64 on the device')
         idx = out if out is not None else torch.empty(B, dtype=torch.int64, device=dev)

@@ -15,7 +15,7 @@ that is neither 0 nor 1 comes back as 1.
 """
 import ctypes
 
-from ._device import get_torch as _torch, stream_ptr
+from ._device import get_torch as _torch, bind_device, check_on, check_tensor, default_device, ptr, stream_ptr
 from ._native import DEFINES, ReplayCfg, ReplayLayout, ReplayRings, check, lib
 from .pyrandom import PyRandom
 
@@ -64,25 +64,11 @@ class ReplayBuffer:
         self._rings = ReplayRings(self._state.data_ptr(), self._next_state.data_ptr(), self._action.data_ptr(),
                                   self._reward.data_ptr(), self._done.data_ptr(), self.count.data_ptr())
 
-    def _device_of(self, t, what):
-        dev = t.device
-        if dev.type != 'cuda':
-            raise ValueError('ReplayBuffer needs %s on the GPU (got %s); there is no CPU fallback' % (what, dev))
-        if self._rings is None and (self.device is None or (self.device.type == 'cuda' and self.device.index is None)):
-            self.device = dev
-        if dev != self.device:
-            raise ValueError('%s is on %s, this ReplayBuffer on %s' % (what, dev, self.device))
-        return dev
-
     def _own_device(self):
-        torch = _torch()
+        """The buffer's device; before any push, the rings are made on the one
+        it was given, or on the current one."""
         if self._rings is None:
-            if not torch.cuda.is_available():
-                raise RuntimeError('ReplayBuffer needs a HIP device (MI355X); there is no CPU fallback')
-            dev = self.device if self.device is not None else torch.device('cuda')
-            if dev.index is None:
-                dev = torch.device('cuda', torch.cuda.current_device())
-            self._allocate(dev)
+            self._allocate(default_device(self.device, 'ReplayBuffer'))
         return self.device
 
     # -------------------------------------------------------------------- API
@@ -98,29 +84,22 @@ class ReplayBuffer:
         torch = _torch()
         S = self.obs_shape[0]
         for name, t in (('obs', obs), ('next_obs', next_obs)):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_contiguous():
-                raise TypeError('ReplayBuffer.push takes %s as a contiguous uint8 tensor' % name)
-            if t.dim() != 5 or tuple(t.shape[1:]) != self.obs_shape:
-                raise ValueError('%s shape %s is not (N,) + %s' % (name, tuple(t.shape), self.obs_shape))
+            check_tensor('ReplayBuffer.push', name, t, 'uint8', (None,) + self.obs_shape, contiguous=True)
         if next_obs.shape[0] != obs.shape[0]:
             raise ValueError('obs holds %d envs, next_obs %d' % (obs.shape[0], next_obs.shape[0]))
         N = obs.shape[0]
-        small = [('actions', actions, (torch.int8,), (N, S)), ('rewards', rewards, (torch.float64,), (N, S)),
-                 ('done', done, (torch.bool, torch.uint8), (N, S))]
+        small = [('actions', actions, 'int8', (N, S)), ('rewards', rewards, 'float64', (N, S)),
+                 ('done', done, ('bool', 'uint8'), (N, S))]
         if skip is not None:
-            small.append(('skip', skip, (torch.bool, torch.uint8), (N, S)))
+            small.append(('skip', skip, ('bool', 'uint8'), (N, S)))
         if step is not None:
-            small.append(('step', step, (torch.int32,), (N,)))
+            small.append(('step', step, 'int32', (N,)))
         for name, t, dtypes, shape in small:
-            if not isinstance(t, torch.Tensor) or t.dtype not in dtypes:
-                raise TypeError('ReplayBuffer.push takes %s as a %s tensor (got %s)' % (
-                    name, ' or '.join(str(d) for d in dtypes), getattr(t, 'dtype', type(t))))
-            if tuple(t.shape) != shape:
-                raise ValueError('%s shape %s is not %s' % (name, tuple(t.shape), shape))
-        dev = self._device_of(obs, 'obs')
+            check_tensor('ReplayBuffer.push', name, t, dtypes, shape)
+        dev = obs.device
+        bind_device(self, dev, 'obs', 'obs is')
         for name, t in [('next_obs', next_obs)] + [(n, t) for n, t, _, _ in small]:
-            if t.device != dev:
-                raise ValueError('%s is on %s, obs on %s' % (name, t.device, dev))
+            check_on(name, t, dev, 'ReplayBuffer')
         if self._rings is None:
             self._allocate(dev)
         actions, rewards = actions.contiguous(), rewards.contiguous()
@@ -134,14 +113,10 @@ class ReplayBuffer:
             lay = ReplayLayout()
             check(self._L.snake_replay_plan(ctypes.byref(self.cfg), N, ctypes.byref(lay)), self._L)
             scratch = self._scratch[N] = torch.empty(int(lay.scratch), dtype=torch.uint8, device=dev)
-        stream = stream_ptr(dev)
-        P = ctypes.c_void_p
         with torch.cuda.device(dev):
             check(self._L.snake_replay_push(
-                ctypes.byref(self.cfg), ctypes.byref(self._rings), P(obs.data_ptr()), P(next_obs.data_ptr()),
-                P(actions.data_ptr()), P(rewards.data_ptr()), P(done.data_ptr()),
-                P(skip.data_ptr()) if skip is not None else None,
-                P(step.data_ptr()) if step is not None else None, N, P(scratch.data_ptr()), stream), self._L)
+                ctypes.byref(self.cfg), ctypes.byref(self._rings), ptr(obs), ptr(next_obs), ptr(actions), ptr(rewards),
+                ptr(done), ptr(skip), ptr(step), N, ptr(scratch), stream_ptr(dev)), self._L)
         self._keep = (obs, next_obs, actions, rewards, done, skip, step)
 
     def size(self):
@@ -205,8 +180,7 @@ class ReplayBuffer:
             if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64 or idx.dim() != 1:
                 raise TypeError('idx must be an int64 (B,) tensor')
             dev = self._own_device()
-            if idx.device != dev:
-                raise ValueError('idx is on %s, this ReplayBuffer on %s' % (idx.device, dev))
+            check_on('idx', idx, dev, 'ReplayBuffer')
             idx = idx.contiguous()
         B = idx.shape[0]
         S, h, w, c = self.obs_shape
@@ -218,13 +192,10 @@ class ReplayBuffer:
         action = torch.empty(B, dtype=torch.int64, device=dev)
         reward = torch.empty(B, dtype=torch.float32, device=dev)
         done = torch.empty(B, dtype=torch.float32, device=dev)
-        stream = stream_ptr(dev)
-        P = ctypes.c_void_p
         with torch.cuda.device(dev):
             check(self._L.snake_replay_gather(
-                ctypes.byref(self.cfg), ctypes.byref(self._rings), P(idx.data_ptr()), B, FORMATS[format],
-                P(state.data_ptr()), P(next_state.data_ptr()), P(action.data_ptr()), P(reward.data_ptr()),
-                P(done.data_ptr()), stream), self._L)
+                ctypes.byref(self.cfg), ctypes.byref(self._rings), ptr(idx), B, FORMATS[format], ptr(state),
+                ptr(next_state), ptr(action), ptr(reward), ptr(done), stream_ptr(dev)), self._L)
         self._keep_idx = idx
         return state, action, reward, next_state, done
 

@@ -24,13 +24,9 @@ from weakref import ref as _weakref
 import numpy as np
 
 from . import spaces
+from ._device import default_device, get_torch as _torch, need_gpu
 from ._native import SnakeLayout, SnakeOut, SnakeState, check, lib
 from .config import build_cfg
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def _raw_stream(index):
@@ -141,8 +137,7 @@ class SnakeVecEnv:
     def __init__(self, num_envs, num_snakes=4, device=None, seed=0, env_offset=0,
                  autoreset=True, coop=False, strict=False, lib_path=None, **env_kwargs):
         torch = _torch()
-        if not torch.cuda.is_available():
-            raise RuntimeError('SnakeVecEnv needs a HIP device (MI355X); there is no CPU fallback')
+        need_gpu('SnakeVecEnv')
         self.num_envs = N = int(num_envs)
         self.cfg, self.meta = build_cfg(num_snakes=num_snakes, coop=coop, autoreset=autoreset,
                                         **env_kwargs)
@@ -155,9 +150,8 @@ class SnakeVecEnv:
         lay = SnakeLayout()
         check(L.snake_plan(ctypes.byref(self.cfg), N, ctypes.byref(lay)))
         self.layout = lay
-        dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-        self._dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
-        self.device = dev = torch.device('cuda', self._dev_index)
+        self.device = dev = default_device(device, 'SnakeVecEnv')     # (after every host-side rejection)
+        self._dev_index = dev.index
         self.obs_shape = (S, lay.obs_h, lay.obs_w, lay.obs_c)
         self.grid_shape = (self.cfg.height, self.cfg.width)
         self.action_n = 5 if self.cfg.observer == 1 else 3
